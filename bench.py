@@ -16,14 +16,22 @@ threshold/top-k keypoint selection — all on the device, through the C ABI.  We
 owns ``--batch`` frames (frame-batch sharding); the only collective is the start-up
 weight broadcast.  Rank 0 prints ONE JSON line.
 
+A plain run sets up, warms up, times the K steps and prints the line (metric, value, unit, ms_per_step, dtype, config).
+--dump-outputs DIR also writes what the last timed step returned (dump_outputs()); the inputs are seeded, so two builds
+can be compared array for array.
+
 Extra objects on that line:
+  collective    (N > 1) the backend and rank count torch.distributed reports, and the one collective of the job: the
+                start-up weight broadcast (bytes, ms)
+and with --full only (each measured in runs of its own after the headline's):
+  precision_modes     the other arithmetic mode, timed the same way (not with --no-precision-modes)
+  one_step_at_a_time  (--in-flight > 1) the same K steps on one stream, each complete before the next starts
   roofline      the dominant kernel (3x3-conv implicit GEMM): algorithmic FLOPs / HIP-event time per launch.  Peak: in
                 the default f16x3 arithmetic one fp32-grade product costs three fp16 MFMAs (v_mfma_f32_16x16x32_f16),
                 so the algorithmic peak is the dense fp16 matrix peak / 3 = 838.9 TFLOP/s; with --precision fp32 it is
                 the fp32 matrix peak 157.3 TFLOP/s (v_mfma_f32_32x32x2_f32)
-  collective    (N > 1) the backend and rank count torch.distributed reports, and the one collective of the job: the
-                start-up weight broadcast (bytes, ms)
-  cpu_baseline  the same workload on the host cores (oracle/torch_port.py, plain torch CPU ops), bounded sample
+  cpu_baseline  (N = 1, not with --no-cpu-baseline) the same workload on the host cores (oracle/torch_port.py, plain
+                torch CPU ops), bounded sample
 """
 from __future__ import annotations
 
@@ -78,7 +86,16 @@ def parse():
                          "dry_run with no throughput in it (checks the launch path on a box without a GPU)")
     ap.add_argument("--backend", default="nccl", help="torch.distributed backend for N>1 (nccl = RCCL; gloo only for "
                                                       "rehearsing the multi-rank path on a single-GPU box)")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline does not need: the other arithmetic mode (precision_modes), the same "
+                         "steps one at a time, the per-kernel HIP-event roofline and the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the timed path returned in its last step as DIR/<name>.npy (float32; arrays above "
+                         "their share of a 48 MB budget as a fixed seeded sample of their flattened elements)")
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    return args
 
 
 def seeded_state_dict(model):
@@ -108,6 +125,33 @@ def kernel_profile(model, x, H, W, steps):
             a["launches"] += 1
     lib.kp2d_set_profiling(eng.handle, 0)
     return agg
+
+
+DUMP_BUDGET_BYTES = 48_000_000
+
+
+def dump_outputs(res, out_dir):
+    """--dump-outputs: the last timed step's results, as the timed path hands them to its caller (``post_processing``'s
+    dict, the selected points / descriptors and their counts), one float32 .npy each.  An array above its share of
+    DUMP_BUDGET_BYTES is written as a fixed seeded sample of its flattened elements (sorted indices, the same for the same
+    shape), so runs with the same arguments write the same elements."""
+    out, pts, desc, cnt = res
+    arrays = {k: v for k, v in out.items() if isinstance(v, torch.Tensor)}
+    arrays.update(keypoints=pts, descriptors=desc, keypoint_count=cnt)
+    os.makedirs(out_dir, exist_ok=True)
+    left, written = DUMP_BUDGET_BYTES // 4, {}
+    for i, (name, t) in enumerate(sorted(arrays.items(), key=lambda kv: (kv[1].numel(), kv[0]))):
+        share = left // (len(arrays) - i)
+        a = t.detach().to("cpu", torch.float32).numpy().reshape(-1)
+        if a.size > share:
+            a = a[np.sort(np.random.default_rng(20240917).choice(a.size, share, replace=False))]
+            written[name] = f"{a.size} of {t.numel()} (sampled)"
+        else:
+            a = a.reshape(tuple(t.shape))
+            written[name] = "x".join(map(str, t.shape))
+        left -= a.size
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    print(f"bench.py: wrote {len(written)} arrays to {out_dir}: {written}", file=sys.stderr, flush=True)
 
 
 def host_cores():
@@ -311,6 +355,74 @@ def dry_run(args, rank, world):
         dist.destroy_process_group()
 
 
+def roofline(model, x, args, B, H, W, fps, world):
+    """--full: per-launch HIP-event figures of the dominant kernel family (a separate profiling forward after the timed
+    steps) against its MFMA peak."""
+    with torch.no_grad():
+        agg = kernel_profile(model, x, H, W, args.profile_steps)
+    dom = max(agg, key=lambda k: agg[k]["ms"])
+    a = agg[dom]
+    achieved = a["flops"] / (a["ms"] * 1e-3) / 1e12
+    total_ms = sum(v["ms"] for v in agg.values())
+    split = "f16x3" in dom
+    # f16x3: one fp32-grade product = three fp16 MFMAs, so the algorithmic peak is the fp16 peak / 3 — for every
+    # split kernel, the attention kernel included (its padded P.V tiles are the kernel's own inefficiency, not a
+    # property of the peak).
+    mfma_per_flop = 1.0 / 3.0
+    peak = PEAK_F16_MFMA_TFLOPS * mfma_per_flop if split else PEAK_F32_MFMA_TFLOPS
+    note = ("dense fp16 MFMA 2516.6 TFLOP/s / 3 MFMAs per fp32-grade product (xh*wh + xh*wl + xl*wh)"
+            if split else "fp32 MFMA v_mfma_f32_32x32x2_f32")
+    roof = {"bound": "mfma", "kernel": dom, "achieved": round(achieved, 2), "peak": round(peak, 1),
+            "unit": "TFLOP/s", "frac": round(achieved / peak, 4), "traffic": None,
+            "peak_note": note,
+            "launches_per_step": a["launches"] // args.profile_steps,
+            "avg_launch_ms": round(a["ms"] / a["launches"], 4),
+            "share_of_kernel_time": round(a["ms"] / total_ms, 4),
+            "algorithmic_gb_per_s": round(a["bytes"] / (a["ms"] * 1e-3) / 1e9, 1),
+            "kernel_ms_per_step": {k: round(v["ms"] / args.profile_steps, 3) for k, v in agg.items()}}
+    # How the pieces fit: the timed steps run the batch as `lanes` sub-batches on that many HIP streams (the tail of
+    # one lane's launch overlaps the next launch of the other); the per-kernel figures above come from a separate
+    # profiling forward that runs ONE lane with HIP events around every launch — the launch shape rocprofv3 sees
+    # under KP2D_LANES=1.  So kernel_ms_sum (one lane, nothing overlapped, forward only) may exceed ms_per_step
+    # (lanes overlapped, plus post_processing / top-k / gather, which are not in the sum).
+    lanes = max(1, min(8, int(os.environ.get("KP2D_LANES", "2"))))
+    roof["lanes"] = 1 if args.in_flight > 1 else min(lanes, B)
+    roof["kernel_ms_sum"] = round(total_ms / args.profile_steps, 3)
+    if args.in_flight > 1:
+        roof["timing_note"] = (f"ms_per_step = time of the K steps / K with {args.in_flight} steps in flight (alternating HIP streams, one engine "
+                               "lane each; forward + post_processing + selection); kernel_ms_per_step / kernel_ms_sum / achieved: "
+                               "single-lane HIP events of the forward's launches, nothing overlapped")
+    else:
+        roof["timing_note"] = (f"ms_per_step: {roof['lanes']} stream lane(s) overlapped, forward + post_processing + selection; "
+                               "kernel_ms_per_step / kernel_ms_sum / achieved: single-lane HIP events of the forward's launches")
+    if split:
+        # a bare fp16 MFMA loop sustains 1571 TFLOP/s on this chip (clock drops to ~1.5 GHz under matrix load:
+        # tools/probes/mfma_f16_probe.hip, profiles/r1_probe_f16.log) -> 523.7 TFLOP/s of fp32-grade products
+        roof["frac_of_sustained_mfma"] = round(achieved / (1571.0 * mfma_per_flop), 4)
+    # HBM-side traffic of the dominant kernel: NOT measured in this run (bench.py cannot run rocprofv3 around
+    # itself).  It is read back from the newest committed PMC pass on this workload (tools/pmc_collect.sh ->
+    # tools/pmc_traffic.py -> profiles/r<round>_traffic.json); the file and the commit that last touched it are named.
+    try:
+        tfile = newest_traffic_file()
+        tr = json.load(open(tfile))
+        if B == 64 and (H, W) == (240, 320) and dom in tr["kernels"]:
+            roof["traffic"] = round(tr["kernels"][dom]["bytes_per_launch"])
+            rel = os.path.relpath(tfile, ROOT)
+            roof["traffic_unit"] = (f"bytes per launch; not measured in this run: PMC FETCH_SIZE x2 + WRITE_SIZE from {rel} "
+                                    f"(git {tr.get('source_commit') or file_commit(rel)}), collected by tools/pmc_collect.sh on this workload")
+            roof["algorithmic_bytes_per_launch"] = round(a["bytes"] / a["launches"])
+        if B == 64 and (H, W) == (240, 320) and split and args.config == "S" and not args.v3:
+            rp = rocprof_conv_frac(a["flops"] / args.profile_steps, peak)
+            if rp:
+                roof["rocprof"] = rp      # (not measured in this run: the committed profiler summary of the same command)
+    except (OSError, KeyError, ValueError, TypeError):
+        pass
+    lb = LAYER_BOUNDARY_MB.get((H, W))
+    if lb and args.config == "S" and not args.v3:
+        roof["hbm_layer_boundary_frac"] = round(fps / world * lb * 1e6 / (PEAK_HBM_GBS * 1e9), 4)
+    return roof
+
+
 def main():
     args = parse()
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
@@ -391,10 +503,11 @@ def main():
 
     from nano_vs_slam_amd.pipeline import BatchStream
 
-    def timed(precision, in_flight=None, key=None):
+    def timed(precision, in_flight=None, key=None, keep=None):
         """W untimed + K timed steps in one arithmetic mode; seconds for the K steps, MAX over ranks.
         in_flight > 1: the same K steps (same kernels, same batch, every step complete before the closing fence), enqueued
-        alternately on that many streams so that consecutive steps overlap (pipeline.BatchStream)."""
+        alternately on that many streams so that consecutive steps overlap (pipeline.BatchStream).
+        keep: a directory to write the last timed step's results to (dump_outputs(), after the closing fence)."""
         in_flight = args.in_flight if in_flight is None else in_flight
         key = key or precision
         model.set_precision(precision)
@@ -405,10 +518,13 @@ def main():
                 run()
             fence()
             t0 = time.perf_counter()
-            for _ in range(args.steps):
+            for _ in range(args.steps - 1):
                 run()
+            last = run()
             fence()
             dt_ = time.perf_counter() - t0
+            if keep:
+                dump_outputs(bs.result(last) if bs is not None else last, keep)
         if bs is not None:
             bs.close()
         t = torch.tensor([dt_], dtype=torch.float64, device=dev)
@@ -420,82 +536,20 @@ def main():
             dist.all_reduce(t, op=dist.ReduceOp.MAX)
         return float(t.item())
 
-    # both arithmetic modes are driver-visible: the headline one (--precision) is `value`; the other is timed the same
-    # way (same K, W, barriers) and reported beside it in `precision_modes`
+    # both arithmetic modes are driver-visible (--full): the headline one (--precision) is `value`; the other is timed the
+    # same way (same K, W, barriers) and reported beside it in `precision_modes`
     other = "fp32" if args.precision == "f16x3" else "f16x3"
     modes = {}
-    if not args.no_precision_modes:
+    if args.full and not args.no_precision_modes:
         modes[other] = timed(other)
-    # one step after the other on one stream (the engine's own two lanes inside each forward), reported beside the headline
-    dt_serial = timed(args.precision, 1, key="serial") if args.in_flight > 1 else None
-    dt = timed(args.precision)
+    # (--full) one step after the other on one stream (the engine's own two lanes inside each forward), beside the headline
+    dt_serial = timed(args.precision, 1, key="serial") if args.full and args.in_flight > 1 else None
+    dt = timed(args.precision, keep=args.dump_outputs if rank == 0 else None)
     modes[args.precision] = dt
 
     if rank == 0:
         frames = global_batch * args.steps
         fps = frames / dt
-        with torch.no_grad():
-            agg = kernel_profile(model, x, H, W, args.profile_steps)
-        dom = max(agg, key=lambda k: agg[k]["ms"])
-        a = agg[dom]
-        achieved = a["flops"] / (a["ms"] * 1e-3) / 1e12
-        total_ms = sum(v["ms"] for v in agg.values())
-        split = "f16x3" in dom
-        # f16x3: one fp32-grade product = three fp16 MFMAs, so the algorithmic peak is the fp16 peak / 3 — for every
-        # split kernel, the attention kernel included (its padded P.V tiles are the kernel's own inefficiency, not a
-        # property of the peak).
-        mfma_per_flop = 1.0 / 3.0
-        peak = PEAK_F16_MFMA_TFLOPS * mfma_per_flop if split else PEAK_F32_MFMA_TFLOPS
-        note = ("dense fp16 MFMA 2516.6 TFLOP/s / 3 MFMAs per fp32-grade product (xh*wh + xh*wl + xl*wh)"
-                if split else "fp32 MFMA v_mfma_f32_32x32x2_f32")
-        roof = {"bound": "mfma", "kernel": dom, "achieved": round(achieved, 2), "peak": round(peak, 1),
-                "unit": "TFLOP/s", "frac": round(achieved / peak, 4), "traffic": None,
-                "peak_note": note,
-                "launches_per_step": a["launches"] // args.profile_steps,
-                "avg_launch_ms": round(a["ms"] / a["launches"], 4),
-                "share_of_kernel_time": round(a["ms"] / total_ms, 4),
-                "algorithmic_gb_per_s": round(a["bytes"] / (a["ms"] * 1e-3) / 1e9, 1),
-                "kernel_ms_per_step": {k: round(v["ms"] / args.profile_steps, 3) for k, v in agg.items()}}
-        # How the pieces fit: the timed steps run the batch as `lanes` sub-batches on that many HIP streams (the tail of
-        # one lane's launch overlaps the next launch of the other); the per-kernel figures above come from a separate
-        # profiling forward that runs ONE lane with HIP events around every launch — the launch shape rocprofv3 sees
-        # under KP2D_LANES=1.  So kernel_ms_sum (one lane, nothing overlapped, forward only) may exceed ms_per_step
-        # (lanes overlapped, plus post_processing / top-k / gather, which are not in the sum).
-        lanes = max(1, min(8, int(os.environ.get("KP2D_LANES", "2"))))
-        roof["lanes"] = 1 if args.in_flight > 1 else min(lanes, B)
-        roof["kernel_ms_sum"] = round(total_ms / args.profile_steps, 3)
-        if args.in_flight > 1:
-            roof["timing_note"] = (f"ms_per_step = time of the K steps / K with {args.in_flight} steps in flight (alternating HIP streams, one engine "
-                                   "lane each; forward + post_processing + selection); kernel_ms_per_step / kernel_ms_sum / achieved: "
-                                   "single-lane HIP events of the forward's launches, nothing overlapped")
-        else:
-            roof["timing_note"] = (f"ms_per_step: {roof['lanes']} stream lane(s) overlapped, forward + post_processing + selection; "
-                                   "kernel_ms_per_step / kernel_ms_sum / achieved: single-lane HIP events of the forward's launches")
-        if split:
-            # a bare fp16 MFMA loop sustains 1571 TFLOP/s on this chip (clock drops to ~1.5 GHz under matrix load:
-            # tools/probes/mfma_f16_probe.hip, profiles/r1_probe_f16.log) -> 523.7 TFLOP/s of fp32-grade products
-            roof["frac_of_sustained_mfma"] = round(achieved / (1571.0 * mfma_per_flop), 4)
-        # HBM-side traffic of the dominant kernel: NOT measured in this run (bench.py cannot run rocprofv3 around
-        # itself).  It is read back from the newest committed PMC pass on this workload (tools/pmc_collect.sh ->
-        # tools/pmc_traffic.py -> profiles/r<round>_traffic.json); the file and the commit that last touched it are named.
-        try:
-            tfile = newest_traffic_file()
-            tr = json.load(open(tfile))
-            if B == 64 and (H, W) == (240, 320) and dom in tr["kernels"]:
-                roof["traffic"] = round(tr["kernels"][dom]["bytes_per_launch"])
-                rel = os.path.relpath(tfile, ROOT)
-                roof["traffic_unit"] = (f"bytes per launch; not measured in this run: PMC FETCH_SIZE x2 + WRITE_SIZE from {rel} "
-                                        f"(git {tr.get('source_commit') or file_commit(rel)}), collected by tools/pmc_collect.sh on this workload")
-                roof["algorithmic_bytes_per_launch"] = round(a["bytes"] / a["launches"])
-            if B == 64 and (H, W) == (240, 320) and split and args.config == "S" and not args.v3:
-                rp = rocprof_conv_frac(a["flops"] / args.profile_steps, peak)
-                if rp:
-                    roof["rocprof"] = rp      # (not measured in this run: the committed profiler summary of the same command)
-        except (OSError, KeyError, ValueError, TypeError):
-            pass
-        lb = LAYER_BOUNDARY_MB.get((H, W))
-        if lb and args.config == "S" and not args.v3:
-            roof["hbm_layer_boundary_frac"] = round(fps / world * lb * 1e6 / (PEAK_HBM_GBS * 1e9), 4)
         line = {
             "metric": "frames/sec KP2DTiny-S 240x320 multitask infer",
             "value": round(fps, 1), "unit": "frames/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
@@ -508,13 +562,14 @@ def main():
                                    f"all heads (score/loc/desc/seg/NetVLAD) + post_processing + top-{args.top_k} selection",
                        "global_batch": global_batch, "frame_shards": world, "n_classes": args.n_classes,
                        "steps_in_flight": args.in_flight},
-            "roofline": roof,
-            "precision_modes": {k: {"value": round(frames / v, 1), "unit": "frames/s",
-                                    "ms_per_step": round(v / args.steps * 1e3, 3),
-                                    "arithmetic": ("split-fp16 operands on v_mfma_f32_16x16x32_f16, fp32 accumulate"
-                                                   if k == "f16x3" else "exact fp32 on v_mfma_f32_32x32x2_f32")}
-                                for k, v in sorted(modes.items())},
         }
+        if args.full:
+            line["roofline"] = roofline(model, x, args, B, H, W, fps, world)
+            line["precision_modes"] = {k: {"value": round(frames / v, 1), "unit": "frames/s",
+                                           "ms_per_step": round(v / args.steps * 1e3, 3),
+                                           "arithmetic": ("split-fp16 operands on v_mfma_f32_16x16x32_f16, fp32 accumulate"
+                                                          if k == "f16x3" else "exact fp32 on v_mfma_f32_32x32x2_f32")}
+                                       for k, v in sorted(modes.items())}
         if dt_serial is not None:
             line["one_step_at_a_time"] = {"value": round(frames / dt_serial, 1), "unit": "frames/s",
                                           "ms_per_step": round(dt_serial / args.steps * 1e3, 3),
@@ -525,7 +580,7 @@ def main():
             fr = rank_fps.get(args.precision, [])
             if fr:
                 line["per_rank_frames_per_s"] = {"min": round(min(fr), 1), "max": round(max(fr), 1)}
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             line["cpu_baseline"] = cpu_baseline(args, sd_np)
             line["speedup_vs_cpu"] = round(fps / line["cpu_baseline"]["value"], 1)
         print(json.dumps(line), flush=True)

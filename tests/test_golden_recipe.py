@@ -40,9 +40,9 @@ def test_recipe_regenerates_committed_fixture_bit_identically(name, tmp_path):
         assert np.array_equal(new[k], old[k]), k
 
 
-@needs_reference
 def test_recipe_refuses_a_model_module_outside_the_reference(tmp_path):
-    """reference_module() must raise when ``src.kp2dtiny.models.kp2dtiny`` is not the reference's file."""
+    """reference_module() must raise when ``src.kp2dtiny.models.kp2dtiny`` is not the reference's file (the module is
+    faked here, so this needs no reference tree)."""
     code = (
         "import importlib.util, sys, types\n"
         f"spec = importlib.util.spec_from_file_location('mg', {os.path.join(ROOT, 'oracle', 'make_golden.py')!r})\n"

@@ -89,7 +89,7 @@ def test_bench_two_ranks_global_batch():
     port = _free_port()
     base = dict(os.environ, MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), WORLD_SIZE="2", HSA_ENABLE_IPC_MODE_LEGACY="0")
     cmd = [sys.executable, "bench.py", "--gpus", "2", "--global-batch", "12", "--steps", "3", "--warmup", "1",
-           "--height", "64", "--width", "96", "--backend", "gloo", "--profile-steps", "1"]
+           "--height", "64", "--width", "96", "--backend", "gloo", "--profile-steps", "1", "--full"]
     outs = _spawn([(cmd, dict(base, RANK=str(r), LOCAL_RANK=str(r))) for r in range(2)])
     for rc, o, e in outs:
         assert rc == 0, e[-3000:]

@@ -6,7 +6,7 @@ OUT=$1; shift
 : > "$OUT"
 for round in 1 2 3; do
   for kv in "$@"; do
-    line=$(env $kv timeout -k 10 200 python3 bench.py --no-cpu-baseline --no-precision-modes --steps 40 2>>"${OUT%.jsonl}.err" | tail -1)
+    line=$(env $kv timeout -k 10 200 python3 bench.py --full --no-cpu-baseline --no-precision-modes --steps 40 2>>"${OUT%.jsonl}.err" | tail -1)
     echo "{\"env\": \"$kv\", \"round\": $round, \"line\": $line}" >> "$OUT"
     python3 - "$kv" "$line" <<'PY'
 import json, sys

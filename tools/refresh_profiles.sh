@@ -17,15 +17,15 @@ errf() { ERRN=$((ERRN + 1)); echo "$OUT/step_${ERRN}.err"; }
 
 if want timed; then
 step "bench line"
-timeout -k 10 300 python3 bench.py 2>"$(errf)" | tail -1 > "$OUT/bench.json"
-timeout -k 10 300 python3 bench.py --steps 1000 --no-cpu-baseline --no-precision-modes 2>"$(errf)" | tail -1 > "$OUT/bench_sustained_1000steps.json"
+timeout -k 10 300 python3 bench.py --full 2>"$(errf)" | tail -1 > "$OUT/bench.json"
+timeout -k 10 300 python3 bench.py --full --steps 1000 --no-cpu-baseline --no-precision-modes 2>"$(errf)" | tail -1 > "$OUT/bench_sustained_1000steps.json"
 cat "$OUT/bench.json" | cut -c1-200
 
 # (timed runs first, profiler passes last: a box that has just run PMC passes measured 3-8 % slower, and short
 # latency-bound runs such as the one-pair matcher up to 1.6x slower)
 step "sweep"
 : > "$OUT/sweep.jsonl"
-sweep() { timeout -k 10 300 python3 bench.py --no-cpu-baseline "$@" 2>"$(errf)" | tail -1 >> "$OUT/sweep.jsonl"; tail -1 "$OUT/sweep.jsonl" | cut -c60-100; }
+sweep() { timeout -k 10 300 python3 bench.py --full --no-cpu-baseline "$@" 2>"$(errf)" | tail -1 >> "$OUT/sweep.jsonl"; tail -1 "$OUT/sweep.jsonl" | cut -c60-100; }
 sweep --height 120 --width 160
 sweep --height 120 --width 160 --in-flight 4      # (short steps: four in flight, profiles/r5_hw_queues.txt)
 sweep
@@ -55,9 +55,9 @@ cut -c1-200 "$OUT/frontend.jsonl"
 fi
 if want prof; then
 step "rocprofv3 kernel stats, the default bench command (two steps in flight: kernels of the two streams overlap, durations are wall time under sharing)"
-timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/stats2" -o r -- python3 bench.py --no-cpu-baseline --no-precision-modes > "$OUT/stats2.log" 2>&1
+timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/stats2" -o r -- python3 bench.py --full --no-cpu-baseline --no-precision-modes > "$OUT/stats2.log" 2>&1
 step "rocprofv3 kernel stats, one step at a time on a single lane (nothing overlaps: the launch shape of bench.py's HIP-event figures)"
-KP2D_LANES=1 timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/stats1" -o r -- python3 bench.py --no-cpu-baseline --no-precision-modes --in-flight 1 > "$OUT/stats1.log" 2>&1
+KP2D_LANES=1 timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/stats1" -o r -- python3 bench.py --full --no-cpu-baseline --no-precision-modes --in-flight 1 > "$OUT/stats1.log" 2>&1
 find "$OUT/stats1" "$OUT/stats2" -name "*kernel_trace.csv" -delete      # only the --stats summaries are kept
 
 step "per-layer tables"

@@ -2,8 +2,8 @@
 """Timeline of the streams of a bench.py run from a rocprofv3 --kernel-trace CSV: which kernels of which HIP stream (queue)
 overlap in time.
 
-    rocprofv3 --kernel-trace --output-format csv -d gpurun_out/trace -o t -- python3 bench.py --steps 8 --warmup 3 --no-cpu-baseline --no-precision-modes
-    python3 tools/trace_lanes.py gpurun_out/trace/t_kernel_trace.csv [AT] > profiles/rN_trace_lanes.txt
+    rocprofv3 --kernel-trace --output-format csv -d rocprof_out/trace -o t -- python3 bench.py --full --steps 8 --warmup 3 --no-cpu-baseline --no-precision-modes
+    python3 tools/trace_lanes.py rocprof_out/trace/t_kernel_trace.csv [AT] > profiles/rN_trace_lanes.txt
 
 AT (default 0.5): where in the run's sequence of forwards the window starts, as a fraction (bench.py times the
 one-step-at-a-time loop first and the steps-in-flight loop second: 0.3 lands in the first, 0.7 in the second).
