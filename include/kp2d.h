@@ -247,10 +247,11 @@ int kp2d_set_chunk_frames(kp2d_model* m, int frames);
  * kernel form).  Keys:
  *   "wsm_min_items"  least number of (16 x 32 pixel tile, 64-channel group) work items of a launch for the
  *                    warp-specialised persistent form of the multi-chunk 3x3 layers (conv3x3_wsm.hip);
- *                    0 = automatic (KP2D_WSM if set, else one item per workgroup of the launch), -1 = never.
+ *                    0 = automatic (more than two rounds of the launch's workgroups), -1 = never.
  *   "ws_min_tiles"   least 16 x 32 pixel tiles of a launch for the warp-specialised form of backbone.conv1b
  *                    (conv3x3_f16x3_ws_kernel); 0 = default (1024).
- *   "wsm_grid"       most workgroups of that form per launch (0 = KP2D_WSM_GRID if set, else CUs / stream lanes).
+ *   "wsm_grid"       most workgroups per launch of the persistent forms (conv3x3_wsm.hip, conv3x3_s16.hip and conv1b's;
+ *                    0 = automatic: CUs / stream lanes, conv1b's form the whole chip).
  *   "lanes"          stream lanes one forward splits its batch over (sub-batches run side by side on internal streams;
  *                    a workspace sized before the change stays valid only for lane counts <= the one it was sized
  *                    for): 0 = default (KP2D_LANES if set, else 2).  A caller that keeps two batches in flight on two
@@ -269,6 +270,10 @@ int kp2d_set_chunk_frames(kp2d_model* m, int frames);
  *                    segmentation head (never under stream capture; the stream is created on first use); 0: in line — and
  *                    the stream is destroyed (a process that keeps several streams busy wants the hardware queue back).
  *   "stem_fusion", "s16_min_items", "multi_launch", "mff_fused": README.md's table of knobs.
+ * Setting a tile-form option back to 0 restores the built-in automatic policy (nano-vs-slam_amd/csrc/conv_policy.h).
+ * KP2D_WSM (0: -1, n: n), KP2D_WSM_GRID, KP2D_WSM_TR, KP2D_S16=0 (s16_min_items -1), KP2D_S16ALL=0 and KP2D_MULTI=0 set
+ * the initial values of "wsm_min_items", "wsm_grid", "wsm_transposed", "s16_min_items", "s16_all" and "multi_launch"
+ * when kp2d_create runs.
  * Unknown keys return KP2D_ERR_ARG.  kp2d_profile_get reports the tile form each conv launch took behind its kernel
  * family ("conv3x3_f16x3<wsm>", "conv3x3_f16x3<2,1,16>", ...). */
 int kp2d_set_option(kp2d_model* m, const char* key, long value);

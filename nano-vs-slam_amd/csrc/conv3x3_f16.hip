@@ -374,7 +374,7 @@ __global__ __launch_bounds__(256, 3) void conv3x3_f16x3_multi_kernel(const ConvM
 // nine weight slots stay in LDS for the whole launch.  One 768-thread workgroup per CU walks tiles g, g + G, ...
 // ---------------------------------------------------------------------------------------------------------------------
 namespace {
-constexpr int WS_TH = 16, WS_TW = 32, WS_PITCH = 36, WS_ROWS = WS_TH + 2, WS_COLS = WS_TW + 2;
+constexpr int WS_TH = PT_TH, WS_TW = PT_TW, WS_PITCH = 36, WS_ROWS = WS_TH + 2, WS_COLS = WS_TW + 2;
 constexpr int WS_LO = WS_ROWS * WS_PITCH * F_PXB;      // byte offset of an image's lo plane (20,736)
 constexpr int WS_IMG = 2 * WS_LO;                      // one input image (41,472 B)
 constexpr int WS_N = 32, WS_WL = 9 * WS_N * 32;        // channels; byte offset of the wl plane behind the wh plane
@@ -965,36 +965,31 @@ int launch_conv1a_mfma(const Conv1aArgs& a, const float* wscale_dev, const unsig
 }
 
 template <bool S16OUT, bool STEM>
-static int launch_ws_t(const ConvArgs& a0, const StemArgs& st, hipStream_t s) {
+static int launch_ws_t(const ConvArgs& a0, const ConvChoice& c, const StemArgs& st, hipStream_t s) {
   ConvArgs a = a0;
-  a.tiles_x = (a.W + WS_TW - 1) / WS_TW;
-  a.tiles_y = (a.H + WS_TH - 1) / WS_TH;
-  const long ntiles = (long)a.tiles_x * a.tiles_y * a.B;
+  a.tiles_x = c.tiles_x; a.tiles_y = c.tiles_y;
   static PerDeviceOnce lds_once;
   if (int e = lds_opt_in(lds_once, reinterpret_cast<const void*>(&conv3x3_f16x3_ws_kernel<S16OUT, STEM>))) return e;
-  const int cus = device_cu_count();
-  static const int grid_env = getenv("KP2D_WSM_GRID") ? atoi(getenv("KP2D_WSM_GRID")) : 0;      // (A/B knob: most workgroups of a persistent launch)
-  const int cap = grid_env > 0 && grid_env < cus ? grid_env : cus;
-  const int grid = (int)(ntiles < cap ? ntiles : cap);
-  hipLaunchKernelGGL((conv3x3_f16x3_ws_kernel<S16OUT, STEM>), dim3(grid), dim3(768),
-                     WS_LDS + (S16OUT ? 8 * WS_BLK : 0) + (STEM ? 4 * 2 * ST_XPL : 0), s, a, st, (int)ntiles);
+  hipLaunchKernelGGL((conv3x3_f16x3_ws_kernel<S16OUT, STEM>), dim3(c.grid), dim3(768),
+                     WS_LDS + (S16OUT ? 8 * WS_BLK : 0) + (STEM ? 4 * 2 * ST_XPL : 0), s, a, st, (int)c.ntiles);
   return (int)hipGetLastError();
 }
 template <bool S16OUT>
-static int launch_ws(const ConvArgs& a, hipStream_t s) {
+static int launch_ws(const ConvArgs& a, const ConvChoice& c, hipStream_t s) {
   if (a.stem_x) {      // conv1a computed by the staging waves (kp2d_api.cpp hands its arguments over instead of launching it)
     const StemArgs st{a.stem_x, a.stem_w, a.stem_scale, a.stem_shift, a.stem_wscale, a.stem_act};
-    return launch_ws_t<S16OUT, true>(a, st, s);
+    return launch_ws_t<S16OUT, true>(a, c, st, s);
   }
-  return launch_ws_t<S16OUT, false>(a, StemArgs{}, s);
+  return launch_ws_t<S16OUT, false>(a, c, StemArgs{}, s);
 }
 
-// the map-side conditions of the warp-specialised conv1b form (the layer-side ones — 16 -> 32 channels, pooled — are the
-// caller's): the plan asks before it decides to keep conv1b's output split (ST_S16P_POOL has no other producer)
-static const bool ws_on = !(getenv("KP2D_WS") && getenv("KP2D_WS")[0] == '0');
-bool conv3x3_ws_would_run(int B, int H, int W, int ws_min) {
-  return ws_on && !(H & 1) && !(W & 1) && W >= 32 && (long)((W + 31) / 32) * ((H + 15) / 16) * B >= (ws_min > 0 ? ws_min : 1024) &&
-         (long)B * H * W * 16 * 4 < 0x7ffffff0L;
+static size_t f_lds_bytes(const ConvArgs& a, int N, int TW, int TH, int slabs) {
+  size_t lds = (size_t)f_w(TW, TH) + (size_t)slabs * 2 * 9 * N * 32;
+  const size_t lds_out = (size_t)N * (TH * TW + 4) * sizeof(float);
+  if (a.store == ST_NCHW && lds_out > lds) lds = lds_out;
+  const size_t lds_tile = (size_t)TH * TW * N * sizeof(float);
+  if (a.store != ST_NCHW && lds_tile > lds) lds = lds_tile;
+  return lds;
 }
 
 template <int NH, int NP, int TH = TILE, bool FLAT32 = false>
@@ -1003,11 +998,7 @@ static int launch_f(const ConvArgs& a0, hipStream_t s) {
   ConvArgs a = a0;
   a.tiles_x = (a.W + TW - 1) / TW;
   a.tiles_y = (a.H + TH - 1) / TH;
-  size_t lds = (size_t)f_w(TW, TH) + (size_t)(NP == 2 ? 2 : 1) * 2 * 9 * N * 32;     // NP = 2: two weight slabs (LDS-DMA)
-  const size_t lds_out = (size_t)N * (TH * TW + 4) * sizeof(float);
-  if (a.store == ST_NCHW && lds_out > lds) lds = lds_out;
-  const size_t lds_tile = (size_t)TH * TW * N * sizeof(float);
-  if (a.store != ST_NCHW && lds_tile > lds) lds = lds_tile;
+  size_t lds = f_lds_bytes(a, N, TW, TH, NP == 2 ? 2 : 1);     // NP = 2: two weight slabs (LDS-DMA)
 #ifdef KP2D_ABLATE
   // Winograd F(2,3) emulation (KP2D_DBG bit 128): its transformed input image and its 12 weight slots need 35 KB more
   if ((a.dbg & 128) && NH == 2) lds += 35 * 1024;
@@ -1023,21 +1014,10 @@ static int launch_f(const ConvArgs& a0, hipStream_t s) {
 
 namespace { thread_local const char* g_variant = ""; }
 
-static size_t f_lds_bytes(const ConvArgs& a, int N, int TW, int TH, int slabs) {
-  size_t lds = (size_t)f_w(TW, TH) + (size_t)slabs * 2 * 9 * N * 32;
-  const size_t lds_out = (size_t)N * (TH * TW + 4) * sizeof(float);
-  if (a.store == ST_NCHW && lds_out > lds) lds = lds_out;
-  const size_t lds_tile = (size_t)TH * TW * N * sizeof(float);
-  if (a.store != ST_NCHW && lds_tile > lds) lds = lds_tile;
-  return lds;
-}
-
 // n <= 4 independent layers, every one a layer the single-frame form <1,1,8> would take (32-channel groups, a grid below 256
 // workgroups); -1000: not all of them are — the caller then launches them one by one
 int launch_conv3x3_f16x3_multi(const ConvArgs* list, int n, hipStream_t s) {
   if (n < 2 || n > 4) return -1000;
-  static const bool multi_on = !(getenv("KP2D_MULTI") && getenv("KP2D_MULTI")[0] == '0');      // (A/B knob)
-  if (!multi_on) return -1000;
   ConvMultiArgs m{};
   m.n = n;
   int gx = 0, gy = 0;
@@ -1046,12 +1026,12 @@ int launch_conv3x3_f16x3_multi(const ConvArgs* list, int n, hipStream_t s) {
     ConvArgs a = list[i];
     if (a.taps != 9 || a.prec != 1 || a.in0.fmt != 0 || a.store == ST_S16P || a.store == ST_S16P_POOL) return -1000;
     if (a.in0.rs != (long)a.W * a.in0.ps || (a.in1.c > 0 && a.in1.rs != (long)a.W * a.in1.ps)) return -1000;
-    if ((long)a.H * a.W * (a.in0.ps > a.in1.ps ? a.in0.ps : a.in1.ps) * 4 >= 0x7ffffff0L) return -1000;
+    if ((long)a.H * a.W * (a.in0.ps > a.in1.ps ? a.in0.ps : a.in1.ps) * 4 >= BUF_LIMIT) return -1000;
     if (!(a.npad == 32 || a.ng32)) return -1000;                       // 32-channel groups (kp2d_api.cpp: small grids)
     a.tiles_x = (a.W + 15) / 16;
     a.tiles_y = (a.H + 7) / 8;
     const int nx = a.tiles_x * a.tiles_y * a.B, ny = a.npad / 32;
-    if ((long)((a.W + 15) / 16) * ((a.H + 15) / 16) * a.B * ny >= 256) return -1000;      // (the condition of the <1,1,8> form)
+    if (!small_grid(a.B, a.H, a.W, ny)) return -1000;      // (the condition of the <1,1,8> form)
     if (a.store == ST_NCHW && ny != 1 && a.act == ACT_SOFTMAX_C) return -1000;
     gx = nx > gx ? nx : gx;
     gy = ny > gy ? ny : gy;
@@ -1068,70 +1048,22 @@ int launch_conv3x3_f16x3_multi(const ConvArgs* list, int n, hipStream_t s) {
 const char* conv3x3_last_variant() { return g_variant; }
 void conv3x3_note_variant(const char* v) { g_variant = v; }
 
+// the tile form conv_policy.h chose
 int launch_conv3x3_f16x3(const ConvArgs& a, hipStream_t s) {
-  if (a.taps != 9 || a.prec != 1) return -1000;
-  // S16P tensors (kp2d_kernels.h): read by conv3x3_s16.hip (32 input channels) and by conv3x3_wsm.hip's IN16 form, written by
-  // both and by the conv1b form below.  No other kernel takes the layout: -1006 is a plan bug
-  if (a.in0.fmt == 1 && a.in1.c == 0 && (a.cin == 32 || a.store == ST_NCHW)) return launch_conv3x3_f16x3_s16(a, s);
-  if (a.wsm_force) {
-    const int e = launch_conv3x3_f16x3_wsm(a, s, 64);
-    return e == -1000 ? -1006 : e;
+  ConvChoice c;
+  if (int e = choose_conv3x3_f16x3(a, device_cu_count(), c)) return e;
+  g_variant = c.variant;
+  switch (c.form) {
+    case FORM_S16: return launch_conv3x3_f16x3_s16(a, c, s);
+    case FORM_WSM: case FORM_WSM32: return launch_conv3x3_f16x3_wsm(a, c, s);
+    case FORM_WS: return a.store == ST_S16P_POOL ? launch_ws<true>(a, c, s) : launch_ws<false>(a, c, s);
+    case FORM_F_2_1_8: return launch_f<2, 1, 8>(a, s);
+    case FORM_F_2_1_16: return launch_f<2, 1>(a, s);
+    case FORM_F_1_2_16: return launch_f<1, 2>(a, s);
+    case FORM_F_1_1_8_FLAT32: return launch_f<1, 1, 8, true>(a, s);
+    case FORM_F_1_1_8: return launch_f<1, 1, 8>(a, s);
+    default: return launch_f<1, 1>(a, s);
   }
-  if (a.in0.fmt == 1 || a.in1.fmt == 1 || a.store == ST_S16P || a.store == ST_S16P_BOTH || a.store == ST_S16P_SHUFFLE || a.store == ST_MIX16) return -1006;
-  if (a.store == ST_S16P_POOL) {
-    if (!(a.cin == 16 && a.in0.c == 16 && a.in1.c == 0 && a.npad == 32 && a.cout == 32 && a.act <= ACT_RELU &&
-          a.in0.rs == (long)a.W * a.in0.ps && a.in0.ps == 16 && a.in0.o == 0 && conv3x3_ws_would_run(a.B, a.H, a.W, a.ws_min))) return -1006;
-    g_variant = a.stem_x ? "<ws>stem+s16" : "<ws>s16";
-    return launch_ws<true>(a, s);
-  }
-  // the staging addresses a source pixel as (y * W + x) * pixel stride
-  if (a.in0.rs != (long)a.W * a.in0.ps || (a.in1.c > 0 && a.in1.rs != (long)a.W * a.in1.ps)) return -1004;
-  if ((long)a.H * a.W * (a.in0.ps > a.in1.ps ? a.in0.ps : a.in1.ps) * 4 >= 0x7ffffff0L) return -1002;
-  if (a.npad != 32 && a.npad % 64 != 0) return -1000;
-  const bool one = a.npad == 32 || a.ng32;
-  if (!one) {
-    // multi-chunk layers with 64-channel groups on grids that fill the chip: warp-specialised persistent form
-    // (conv3x3_wsm.hip; policy and overrides at its launcher)
-    {
-      const int e = launch_conv3x3_f16x3_wsm(a, s, 64);
-      if (e != -1000) return e;      // (the launcher noted "<wsm>" or, for the transposed walk, "<wsm>t")
-    }
-    // map heights that leave the last 16-row tile row at most half full (120 = 7.5 x 16): 8 x 32 tiles, no ragged row
-    static const bool flat_on = !(getenv("KP2D_FLAT") && getenv("KP2D_FLAT")[0] == '0');
-    const int rag = a.H & 15;
-    if (flat_on && rag >= 1 && rag <= 8 && a.W >= 32 && (long)a.H * a.W < (1L << 20)) { g_variant = "<2,1,8>"; return launch_f<2, 1, 8>(a, s); }
-    g_variant = "<2,1,16>";
-    return launch_f<2, 1>(a, s);
-  }
-  // 32-channel layers on grids that fill the chip anyway: 16 x 32 pixel tiles (one weight slab per 512 pixels, 16 waves
-  // per CU).  Small grids keep the 16 x 16 tiles (twice the workgroups, half as long: single frames).  KP2D_WIDE=0: never.
-  // single-chunk, max-pooled, 32 channels (conv1b) on grids that fill the chip several times: warp-specialised persistent form
-  if (ws_on && a.cin == 16 && a.in0.c == 16 && a.in1.c == 0 && a.npad == 32 && a.store == ST_NHWC_POOL && a.act <= ACT_RELU &&
-      !(a.H & 1) && !(a.W & 1) && a.W >= 32 && (long)((a.W + 31) / 32) * ((a.H + 15) / 16) * a.B >= (a.ws_min > 0 ? a.ws_min : 1024) &&
-      (long)a.B * a.in0.bs * 4 < 0x7ffffff0L)
-  { g_variant = a.stem_x ? "<ws>stem" : "<ws>"; return launch_ws<false>(a, s); }
-  // 32-channel layers on grids that fill the chip several times: the warp-specialised persistent form with 32-channel items
-  if (a.npad == 32 && !a.ng32) {
-    const int e = launch_conv3x3_f16x3_wsm(a, s, 32);
-    if (e != -1000) return e;
-  }
-  static const bool wide_on = !(getenv("KP2D_WIDE") && getenv("KP2D_WIDE")[0] == '0');
-  const long wide_tiles = (long)((a.W + 31) / 32) * a.tiles_y * a.B * (a.npad / 32);
-  // (planar API outputs keep the 16-pixel tiles: measured 0.148 -> 0.151 ms on desc_head.confBb with the wide ones)
-  if (wide_on && a.store != ST_NCHW && a.W >= 32 && wide_tiles >= 1024 && (long)a.H * a.W < (1L << 20)) { g_variant = "<1,2,16>"; return launch_f<1, 2>(a, s); }
-  // planar outputs on maps with a half-empty last 16-row tile row (confBb / the class map at 120 rows): 8 x 32 tiles
-  {
-    static const bool flat_on = !(getenv("KP2D_FLAT") && getenv("KP2D_FLAT")[0] == '0');
-    const int rag = a.H & 15;
-    if (flat_on && a.store == ST_NCHW && rag >= 1 && rag <= 8 && a.W >= 32 && !(a.W & 3) && (long)a.H * a.W < (1L << 20) &&
-        (long)((a.W + 31) / 32) * ((a.H + 7) / 8) * a.B * (a.npad / 32) >= 512)
-    { g_variant = "<1,1,8,flat32>"; return launch_f<1, 1, 8, true>(a, s); }
-  }
-  // single frames (the grid of 16 x 16 tiles would leave most CUs idle): 8-row tiles, twice the workgroups, half as long
-  static const bool short_on = !(getenv("KP2D_SHORT") && getenv("KP2D_SHORT")[0] == '0');
-  if (short_on && (long)a.tiles_x * a.tiles_y * a.B * (a.npad / 32) < 256) { g_variant = "<1,1,8>"; return launch_f<1, 1, 8>(a, s); }
-  g_variant = "<1,1,16>";
-  return launch_f<1, 1>(a, s);
 }
 
 }  // namespace kp2d

@@ -32,7 +32,6 @@
 // waves of a role.
 #include "conv_common.h"
 #include "device_guard.h"
-#include <cstdlib>
 #include <type_traits>
 
 namespace kp2d {
@@ -40,7 +39,7 @@ namespace kp2d {
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 namespace {
-constexpr int D_TH = 16, D_TW = 32, D_PITCH = 36, D_ROWS = D_TH + 2, D_COLS = D_TW + 2, D_PXB = 32;
+constexpr int D_TH = PT_TH, D_TW = PT_TW, D_PITCH = 36, D_ROWS = D_TH + 2, D_COLS = D_TW + 2, D_PXB = 32;
 constexpr int D_LO = D_ROWS * D_PITCH * D_PXB;         // byte offset of an image's lo plane (20,736)
 constexpr int D_IMG = 2 * D_LO;                        // one input image: hi plane | lo plane (41,472 B)
 constexpr int D_NPIECE = (D_IMG + 1023) / 1024;        // 1-KiB LDS-DMA pieces of an image (41: the last one is half a piece)
@@ -461,53 +460,6 @@ __global__ __launch_bounds__(D_THREADS, 3) void conv3x3_f16x3_s16_kernel(const C
 }
 
 // ---- launch side -----------------------------------------------------------------------------------------------------
-static bool s16_eligible(const ConvArgs& a) {
-  if (a.taps != 9 || a.prec != 1 || a.in0.fmt != 1 || a.in1.c != 0 || a.in0.c != a.cin || a.in0.o != 0) return false;
-  if (a.store == ST_NCHW) {
-    // planar logits behind a 64-channel S16P tensor (confBb, convs.8): one 32-channel group, every channel into out0
-    if (a.cin != 64 || a.npad != 32 || a.act != ACT_NONE || a.nsplit != a.cout || a.W < 32 || (a.W & 3) || a.ids_out) return false;
-    if (a.in0.bs != (long)a.H * a.W * a.cin || (long)a.H * a.W * a.cin * 4 >= 0x7ffffff0L) return false;
-    return true;
-  }
-  if (a.cin != 32) return false;
-  if (a.act > ACT_RELU || a.W < 32 || (a.cout & 15)) return false;
-  if (a.store == ST_S16P) { if (a.npad != 32) return false; }
-  else if (a.store == ST_NHWC || a.store == ST_NHWC_POOL || a.store == ST_NHWC_BOTH || a.store == ST_S16P_BOTH) { if (a.npad != 64) return false; }
-  else return false;
-  if ((a.store == ST_NHWC_POOL || a.store == ST_NHWC_BOTH || a.store == ST_S16P_BOTH) && ((a.H | a.W) & 1)) return false;
-  if (a.in0.bs != (long)a.H * a.W * a.cin) return false;                      // dense S16P frames
-  if ((long)a.H * a.W * a.cin * 4 >= 0x7ffffff0L) return false;
-  const long os = (a.store == ST_S16P || a.store == ST_S16P_BOTH) ? a.cout : (a.os0 > a.os1 ? a.os0 : a.os1);
-  if ((long)a.H * a.W * os * 4 >= 0x7ffffff0L) return false;
-  return true;
-}
-
-// workgroups a launch of `nitems` items takes with `lanes` stream lanes side by side (whole rounds, a multiple of 8: contiguous
-// runs per XCD), 0: too few items for the form (automatic: at least three rounds, as conv3x3_wsm.hip) — shared by the launcher
-// and by the plan, which must know BEFORE it picks the activation layout whether the form will run
-static int s16_grid(long nitems, int lanes, int min_items, int grid_opt) {
-  const int cus = device_cu_count();
-  static const int grid_env = getenv("KP2D_WSM_GRID") ? atoi(getenv("KP2D_WSM_GRID")) : 0;      // (the same knob as conv3x3_wsm.hip)
-  int cap = grid_opt > 0 ? grid_opt : (grid_env > 0 ? grid_env : cus / (lanes > 1 ? lanes : 1));
-  if (cap > cus) cap = cus;
-  cap &= ~7;
-  if (cap < 8) return 0;
-  const long need = min_items > 0 ? min_items : 2L * cap + 1;
-  if (nitems < need || nitems >= (1L << 30)) return 0;
-  const long rounds = (nitems + cap - 1) / cap;
-  int grid = (int)(((nitems + rounds - 1) / rounds + 7) & ~7L);
-  if (grid > cap) grid = cap;
-  if (grid > nitems) grid = (int)(nitems & ~7L);
-  return grid < 8 ? 0 : grid;
-}
-
-bool conv3x3_s16_would_run(int B, int H, int W, int lanes, int min_items, int grid_opt) {
-  static const bool off = getenv("KP2D_S16") && getenv("KP2D_S16")[0] == '0';      // (A/B knob)
-  if (off || min_items < 0 || W < 32 || ((H | W) & 1)) return false;
-  const long nitems = (long)((W + D_TW - 1) / D_TW) * ((H + D_TH - 1) / D_TH) * B;
-  return s16_grid(nitems, lanes, min_items, grid_opt) > 0;
-}
-
 template <int STORE, int NN, int NCH = 2>
 static int s16_launch_one(const ConvArgs& a, int grid, long nitems, hipStream_t s) {
   static PerDeviceOnce lds_once;      // per instantiation and device
@@ -516,25 +468,17 @@ static int s16_launch_one(const ConvArgs& a, int grid, long nitems, hipStream_t 
   return (int)hipGetLastError();
 }
 
-// -1000: not a layer of this form; -1006: the plan handed an S16P input to a launch the form cannot take (a plan bug:
-// there is no other kernel that reads that layout)
-int launch_conv3x3_f16x3_s16(const ConvArgs& a0, hipStream_t s) {
-  if (a0.in0.fmt != 1) return -1000;
-  if (!s16_eligible(a0)) return -1006;
+// what conv_policy.h choose_s16() chose
+int launch_conv3x3_f16x3_s16(const ConvArgs& a0, const ConvChoice& c, hipStream_t s) {
   ConvArgs a = a0;
-  a.tiles_x = (a.W + D_TW - 1) / D_TW;
-  a.tiles_y = (a.H + D_TH - 1) / D_TH;
-  const long nitems = (long)a.tiles_x * a.tiles_y * a.B;
-  const int grid = s16_grid(nitems, a.wsm_lanes, a.s16_min, a.wsm_grid);
-  if (grid == 0) return -1006;
-  conv3x3_note_variant(a.store == ST_NCHW ? "<s16>planar" : "<s16>");
+  a.tiles_x = c.tiles_x; a.tiles_y = c.tiles_y;
   switch (a.store) {
-    case ST_NCHW: return s16_launch_one<ST_NCHW, 2, 4>(a, grid, nitems, s);
-    case ST_S16P: return s16_launch_one<ST_S16P, 2>(a, grid, nitems, s);
-    case ST_NHWC: return s16_launch_one<ST_NHWC, 4>(a, grid, nitems, s);
-    case ST_NHWC_BOTH: return s16_launch_one<ST_NHWC_BOTH, 4>(a, grid, nitems, s);
-    case ST_S16P_BOTH: return s16_launch_one<ST_S16P_BOTH, 4>(a, grid, nitems, s);
-    default: return s16_launch_one<ST_NHWC_POOL, 4>(a, grid, nitems, s);
+    case ST_NCHW: return s16_launch_one<ST_NCHW, 2, 4>(a, c.grid, c.nitems, s);
+    case ST_S16P: return s16_launch_one<ST_S16P, 2>(a, c.grid, c.nitems, s);
+    case ST_NHWC: return s16_launch_one<ST_NHWC, 4>(a, c.grid, c.nitems, s);
+    case ST_NHWC_BOTH: return s16_launch_one<ST_NHWC_BOTH, 4>(a, c.grid, c.nitems, s);
+    case ST_S16P_BOTH: return s16_launch_one<ST_S16P_BOTH, 4>(a, c.grid, c.nitems, s);
+    default: return s16_launch_one<ST_NHWC_POOL, 4>(a, c.grid, c.nitems, s);
   }
 }
 

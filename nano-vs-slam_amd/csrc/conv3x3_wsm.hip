@@ -26,7 +26,6 @@
 // workgroup executes every barrier, and no barrier sits under a condition that differs between waves of a role.
 #include "conv_common.h"
 #include "device_guard.h"
-#include <cstdlib>
 #include <type_traits>
 
 namespace kp2d {
@@ -34,7 +33,7 @@ namespace kp2d {
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 namespace {
-constexpr int M_TH = 16, M_TW = 32, M_PITCH = 36, M_ROWS = M_TH + 2, M_COLS = M_TW + 2, M_PXB = 32;
+constexpr int M_TH = PT_TH, M_TW = PT_TW, M_PITCH = 36, M_ROWS = M_TH + 2, M_COLS = M_TW + 2, M_PXB = 32;
 constexpr int M_LO = M_ROWS * M_PITCH * M_PXB;         // byte offset of an image's lo plane (20,736)
 constexpr int M_IMG = 2 * M_LO;                        // one input image: hi plane | lo plane (41,472 B)
 // N = channels per work item: 64 (four 16-channel N-tiles per multiplying wave) or 32 (two; the 32-channel layers)
@@ -42,7 +41,6 @@ __host__ __device__ constexpr int m_wl(int n) { return 9 * n * 32; }            
 __host__ __device__ constexpr int m_wslab(int n) { return 2 * m_wl(n); }              // a chunk's weight slab (36,864 B)
 __host__ __device__ constexpr int m_stage(int n) { return M_IMG + m_wslab(n); }       // one stage: image | weights (78,336 B)
 __host__ __device__ constexpr int m_ss(int n) { return 2 * m_stage(n); }              // scale | shift vectors behind the two stages (156,672)
-constexpr int M_MAXN = 320;                            // channels of a layer (scale / shift in LDS; 320 = the five heads' first layers as one)
 __host__ __device__ constexpr int m_lds(int n) { return m_ss(n) + 2 * M_MAXN * 4; }   // 159,232 B / 122,368 B
 constexpr int M_G = M_ROWS * M_COLS * 4;               // 16-byte granules of a halo image (2448)
 constexpr int M_PT = 256;                              // staging threads
@@ -89,7 +87,7 @@ __global__ __launch_bounds__(M_THREADS, 3) void conv3x3_f16x3_wsm_kernel(const C
   // only the two places that form global addresses know: the staging waves' pixel index and the epilogue's (y, x).
   // Why: a 30 x 40 map is 2 x 2 tiles with 8 of the second tile column's 32 columns inside (24 quarter-SIMD units of matrix
   // work per frame for 18.75 of pixels); as 40 x 30 it is 3 x 1 tiles, the last with 8 of 16 rows = half of the waves, none
-  // of them multiplying padding (20 units).  The launcher picks the cheaper walk per layer (wsm_walk_cost).
+  // of them multiplying padding (20 units).  conv_policy.h picks the cheaper walk per layer (wsm_walk_cost).
   const bool tr = a.wsm_tr != 0;
   const int H = tr ? a.W : a.H, W = tr ? a.H : a.W;
   const int Wg = a.W;                                // pixels per row of the map in memory
@@ -617,58 +615,6 @@ __global__ __launch_bounds__(M_THREADS, 3) void conv3x3_f16x3_wsm_kernel(const C
   if (due) finish(prev);                             // (the barriers are behind us: no wave waits for this)
 }
 
-// true when the layer can run as the kernel above (launch_conv3x3_f16x3 falls back to the general kernel otherwise)
-static bool wsm_eligible(const ConvArgs& a, int N) {
-  if (a.taps != 9 || a.prec != 1 || a.ng32 || a.npad % N != 0 || a.npad > M_MAXN) return false;
-  const bool s16out = a.store == ST_S16P || a.store == ST_S16P_SHUFFLE || a.store == ST_MIX16;
-  if (a.store != ST_NHWC && a.store != ST_SHUFFLE && a.store != ST_NHWC_BOTH && a.store != ST_NHWC_POOL && !s16out) return false;
-  if (a.act > ACT_RELU) return false;
-  if (((a.in0.c | a.cin) & 15) != 0 || a.cin < 32) return false;      // whole 16-channel chunks, never straddling the sources
-  if (a.cout & 3) return false;
-  if (a.store == ST_SHUFFLE && ((a.cout >> 2) & 15)) return false;      // a 16-channel N-tile is one sub-pixel
-  if (a.W < 32) return false;
-  const long ps = a.in0.ps > a.in1.ps ? a.in0.ps : a.in1.ps;
-  if ((long)a.H * a.W * ps * 4 >= 0x7ffffff0L) return false;
-  if (a.in0.fmt == 1) {
-    // S16P sources: whole chunks of dense tensors (a view is a run of chunks: ps = the tensor's channels)
-    if (N != 64 || (a.in1.c > 0 && a.in1.fmt != 1) || ((a.in0.o | a.in1.o) & 15)) return false;
-    if (a.in0.bs != (long)a.H * a.W * a.in0.ps || (a.in1.c > 0 && a.in1.bs != (long)a.H * a.W * a.in1.ps)) return false;
-  } else {
-    if (a.in1.c > 0 && a.in1.fmt == 1) return false;
-    if (a.in0.rs != (long)a.W * a.in0.ps || (a.in1.c > 0 && a.in1.rs != (long)a.W * a.in1.ps)) return false;
-  }
-  if (s16out) {
-    // whole chunks out, 64-channel items, a pair of N-tiles = 32 channels of one sub-pixel
-    if (N != 64 || (a.cout & 15)) return false;
-    if (a.store == ST_S16P_SHUFFLE && (((a.cout >> 2) & 31) || (a.os0 & 15) || (a.oo0 & 15))) return false;
-    if (a.store == ST_S16P && ((a.os0 & 15) || (a.oo0 & 15))) return false;
-    if (a.store == ST_MIX16 && ((a.nsplit & 63) || a.nsplit <= 0 || a.nsplit >= a.cout || (a.os1 & 15) || (a.oo1 & 15) || (a.os0 & 3))) return false;
-  }
-  const long up = (a.store == ST_SHUFFLE || a.store == ST_S16P_SHUFFLE) ? 4 : 1;
-  if ((long)a.H * a.W * up * a.os0 * 4 >= 0x7ffffff0L) return false;
-  if (a.store == ST_MIX16 && (long)a.H * a.W * a.os1 * 4 >= 0x7ffffff0L) return false;
-  return true;
-}
-
-// Matrix time of one map walked as Ht x Wt in tile space, in units of one wave's four M-tiles: a multiplying wave (wr, ph)
-// works when its 4 rows x 16 columns touch the map, SIMD s holds waves s and s + 4 = (wr s, ph 0) and (wr (s + 2) & 3, ph 1),
-// and a step lasts as long as its busiest SIMD.  (What the model leaves out — staging, the barrier — is the same per step, and
-// the cheaper walk never has more steps.)
-static int wsm_walk_cost(int Ht, int Wt) {
-  int cost = 0;
-  for (int y0 = 0; y0 < Ht; y0 += M_TH)
-    for (int x0 = 0; x0 < Wt; x0 += M_TW) {
-      int worst = 0;
-      for (int sd = 0; sd < 4; ++sd) {
-        const int b0 = (y0 + 4 * sd < Ht) ? 1 : 0;                                         // ph 0: its 16 columns start at x0
-        const int b1 = (y0 + 4 * ((sd + 2) & 3) < Ht && x0 + 16 < Wt) ? 1 : 0;
-        worst = b0 + b1 > worst ? b0 + b1 : worst;
-      }
-      cost += worst;
-    }
-  return cost;
-}
-
 template <int STORE, int NN, bool IN16 = false>
 static int wsm_launch_one(const ConvArgs& a, int grid, long nitems, long ntiles, hipStream_t s) {
   static PerDeviceOnce lds_once;      // per instantiation and device
@@ -701,86 +647,12 @@ static int wsm_launch(const ConvArgs& a, int grid, long nitems, long ntiles, hip
   }
 }
 
-// Policy.  A workgroup of this form fills its CU's LDS, so launches of two stream lanes can only run side by side on
-// DISJOINT CUs: with L lanes a launch takes at most cap = CUs / L workgroups (kp2d_api.cpp passes L; a profiling forward
-// runs one lane and takes the whole chip).  The form is used when a launch has more than TWO rounds of work items for that
-// grid — at one item per workgroup nothing is left to overlap and the general kernels are as fast or faster (30 x 40 maps:
-// 0.031 / 0.047 ms general against 0.032 / 0.052 ms, profiles/r4_layers_wsm_vs_general.txt) — and the grid is sized for whole rounds:
-// rounds = ceil(items / cap), grid = ceil(items / rounds) rounded up to a multiple of 8 (192 items on a cap of 128 run
-// as 2 rounds on 96 workgroups, not 1.5 rounds on 128: the first automatic policy lost 5 % at 32 frames and 20 % at
-// 120 x 160 frames that way, profiles/r4_sweep_first_policy.jsonl).  Overrides: ConvArgs::wsm_min / wsm_grid
-// (kp2d_set_option), else KP2D_WSM (0 = never, N = least items) and KP2D_WSM_GRID.
-// n_item = 64: layers packed in 64-channel groups; 32: the 32-channel layers (npad = 32; automatic use only with KP2D_WSM32=1).
-int launch_conv3x3_f16x3_wsm(const ConvArgs& a0, hipStream_t s, int n_item) {
-  static const long min_env = getenv("KP2D_WSM") ? atol(getenv("KP2D_WSM")) : -1;      // -1: automatic
-  static const int grid_env = getenv("KP2D_WSM_GRID") ? atoi(getenv("KP2D_WSM_GRID")) : 0;
-  // 32-channel items are correct (bit-identical, tested through kp2d_set_option) but not faster: conv2a / 2b / 3a 0.088-0.094 ms
-  // against 0.087-0.089 ms on the wide LDS-DMA tiles, -0.8 % end to end (profiles/r4_ab_wsm32.txt) — automatic use is off
-  static const bool n32_on = getenv("KP2D_WSM32") && getenv("KP2D_WSM32")[0] == '1';
-  const bool forced = a0.wsm_force != 0;      // S16P in or out: the plan already asked conv3x3_wsm_would_run; no other kernel takes the layout
-  if (!forced && (a0.wsm_min < 0 || (a0.wsm_min == 0 && min_env == 0))) return -1000;
-  if (n_item != 64 && n_item != 32) return forced ? -1006 : -1000;
-  if (!wsm_eligible(a0, n_item)) return forced ? -1006 : -1000;
+// what conv_policy.h choose_wsm() chose (n_item 32 or 64, walk, grid, items)
+int launch_conv3x3_f16x3_wsm(const ConvArgs& a0, const ConvChoice& c, hipStream_t s) {
   ConvArgs a = a0;
-  // Transposed walk (tile rows = map columns; needs the layer's transposed-tap pack).  OFF unless asked for: it sums the nine
-  // taps in another order than every other form, and the engine's results are bit-identical whatever the batch size, lane
-  // count or tile form — a walk chosen by grid size would break that.  ConvArgs::wsm_tr in (kp2d_set_option
-  // "wsm_transposed", else KP2D_WSM_TR): 0 never, 1 always, 2 where the matrix-time model says it is cheaper; out: the decision.
-  static const int tr_env = getenv("KP2D_WSM_TR") ? atoi(getenv("KP2D_WSM_TR")) : 0;
-  const int tr_mode = a0.wsm_tr != 0 ? a0.wsm_tr : tr_env;
-  a.wsm_tr = 0;
-  const bool s16_any = a.in0.fmt == 1 || a.store == ST_S16P || a.store == ST_S16P_SHUFFLE || a.store == ST_MIX16;      // S16P rows are map rows
-  if (n_item == 64 && a.w_tr && tr_mode > 0 && !s16_any && a.H >= 16 && (tr_mode == 1 || wsm_walk_cost(a.W, a.H) < wsm_walk_cost(a.H, a.W))) {
-    a.wsm_tr = 1;
-    a.w = a.w_tr;
-  }
-  const int Ht = a.wsm_tr ? a.W : a.H, Wt = a.wsm_tr ? a.H : a.W;
-  a.tiles_x = (Wt + M_TW - 1) / M_TW;
-  a.tiles_y = (Ht + M_TH - 1) / M_TH;
-  const long ntiles = (long)a.tiles_x * a.tiles_y * a.B;
-  const long nitems = ntiles * (a.npad / n_item);
-  const int cus = device_cu_count();
-  const int lanes = a.wsm_lanes > 1 ? a.wsm_lanes : 1;
-  int cap = a.wsm_grid > 0 ? a.wsm_grid : (grid_env > 0 ? grid_env : cus / lanes);
-  if (cap > cus) cap = cus;
-  cap &= ~7;                                                   // a multiple of 8: contiguous runs per XCD
-  const bool automatic = a.wsm_min == 0 && min_env < 0;
-  // automatic: at least three rounds of work per workgroup (the form's start-up — two steps of loads before the first
-  // product — and its drain are paid per launch: at 32 frames, 192 items per lane, it lost 7 % end to end) and, for the
-  // 64-channel items, at least four chunks (conv3b, two chunks and two stores per item, is slower in this form: 0.165
-  // against 0.157 ms)
-  const long min_items = a.wsm_min > 0 ? a.wsm_min : (min_env > 0 ? min_env : 2 * cap + 1);
-  if (cap < 8 || nitems >= (1L << 30)) return forced ? -1006 : -1000;
-  if (!forced) {
-    if (nitems < min_items) return -1000;
-    if (automatic && n_item == 64 && a.cin < 64) return -1000;
-    if (automatic && n_item == 32 && !n32_on) return -1000;
-  }
-  const long rounds = (nitems + cap - 1) / cap;
-  int grid = (int)(((nitems + rounds - 1) / rounds + 7) & ~7L);
-  if (grid > cap) grid = cap;
-  if (grid > nitems) grid = (int)(nitems & ~7L);
-  if (grid < 8) return forced ? -1006 : -1000;
-  conv3x3_note_variant(n_item == 32 ? "<wsm32>" : (a.wsm_tr ? "<wsm>t" : (a.in0.fmt == 1 ? (s16_any && a.store != ST_NHWC && a.store != ST_NHWC_POOL ? "<wsm>s16io" : "<wsm>s16in") : (s16_any ? "<wsm>s16out" : "<wsm>"))));      // (what the engine's profile records)
-  return n_item == 64 ? wsm_launch<4>(a, grid, nitems, ntiles, s) : wsm_launch<2>(a, grid, nitems, ntiles, s);
-}
-
-// the automatic policy above for a 64-channel-group layer (the plan fixes the S16P layout of the big-grid forward on the
-// answer for its smallest such layer, backbone.conv4a)
-// full_rounds: the automatic policy asks for more than this many full rounds of work items (2: the register-staging form;
-// 1: the S16P-input form, whose start-up is one LDS-DMA round trip instead of two steps of loads — 32 frames of 240 x 320,
-// 384 items on 256 workgroups: 22.8k -> 23.1k frames/s with the layout on, profiles/r5_ab_s16_all.txt)
-bool conv3x3_wsm_would_run(int B, int H, int W, int groups, int lanes, int wsm_min, int grid_opt, int full_rounds) {
-  static const long min_env = getenv("KP2D_WSM") ? atol(getenv("KP2D_WSM")) : -1;
-  static const int grid_env = getenv("KP2D_WSM_GRID") ? atoi(getenv("KP2D_WSM_GRID")) : 0;
-  if (wsm_min < 0 || (wsm_min == 0 && min_env == 0) || W < 32) return false;
-  const int cus = device_cu_count();
-  int cap = grid_opt > 0 ? grid_opt : (grid_env > 0 ? grid_env : cus / (lanes > 1 ? lanes : 1));
-  if (cap > cus) cap = cus;
-  cap &= ~7;
-  const long nitems = (long)((W + M_TW - 1) / M_TW) * ((H + M_TH - 1) / M_TH) * B * groups;
-  const long min_items = wsm_min > 0 ? wsm_min : (min_env > 0 ? min_env : full_rounds * cap + 1);
-  return cap >= 8 && nitems >= min_items && nitems < (1L << 30);
+  a.wsm_tr = c.walk; a.w = c.walk ? a.w_tr : a.w;
+  a.tiles_x = c.tiles_x; a.tiles_y = c.tiles_y;
+  return c.form == FORM_WSM ? wsm_launch<4>(a, c.grid, c.nitems, c.ntiles, s) : wsm_launch<2>(a, c.grid, c.nitems, c.ntiles, s);
 }
 
 }  // namespace kp2d

@@ -145,9 +145,9 @@ struct kp2d_model {
   bool finalized = false;
   int chunk_frames = 0;
   int ws_min = 0;         // kp2d_set_option("ws_min_tiles"): least tiles of a launch for the warp-specialised conv1b form (0 = 1024)
-  int wsm_grid = 0;       // kp2d_set_option("wsm_grid"): most workgroups per launch of that form (0 = KP2D_WSM_GRID or one per CU)
+  int wsm_grid = 0;       // kp2d_set_option("wsm_grid"): most workgroups per launch of the persistent forms (0 = one per CU and lane)
   int wsm_tr = 0;         // kp2d_set_option("wsm_transposed")
-  int wsm_min = 0;        // kp2d_set_option("wsm_min_items"): 0 = automatic (KP2D_WSM, else one item per workgroup), < 0 = never (conv3x3_wsm.hip)
+  int wsm_min = 0;        // kp2d_set_option("wsm_min_items"): 0 = automatic (conv_policy.h), < 0 = never (conv3x3_wsm.hip)
   bool mff_fused = !(getenv("KP2D_MFF") && getenv("KP2D_MFF")[0] == '0');   // kp2d_set_option("mff_fused"): MixFeedForward's tail as one launch (mff_tail.hip)
   // kp2d_set_option("stem_fusion") / KP2D_STEM: the first layer — 1 (default): split-fp16 products, computed inside conv1b's launch on
   // big grids (conv3x3_f16.hip STEM) and by conv1a_mfma_kernel otherwise (the same bits); 2: the same arithmetic, never fused; 0: round 4's
@@ -174,8 +174,6 @@ struct kp2d_model {
   std::string tap_name;   // kp2d_set_tap: one intermediate activation copied out (planar) during forward
   float* tap_dst = nullptr;
   size_t tap_cap = 0;
-  bool head_dot = !(getenv("KP2D_HEAD_DOT") && getenv("KP2D_HEAD_DOT")[0] == '0');   // KP2D_HEAD_DOT=0: heads on the matrix-core kernels (A/B)
-  bool small_grid_ng32 = !(getenv("KP2D_NG32") && getenv("KP2D_NG32")[0] == '0');   // KP2D_NG32=0: always 64-channel groups
   std::vector<ProfRec> prof;
   size_t prof_used = 0;
   hipStream_t prof_stream = nullptr;
@@ -713,7 +711,7 @@ struct Plan {
     a.wsm_lanes = nlanes;
     a.s16_min = m->s16_min;
     // S16P tensors beyond the 32-channel stage are read and written by conv3x3_wsm.hip only: build() fixed the layout
-    // after asking conv3x3_wsm_would_run, the launcher then skips its item-count policy
+    // after asking wsm_would_run (conv_policy.h), which then skips its item-count policy
     a.wsm_force = ((s0.fmt == 1 && !(c.cin == 32 && s1.c == 0) && store != ST_NCHW) || store == ST_S16P_SHUFFLE || store == ST_MIX16 ||
                    (store == ST_S16P && c.npad >= 64)) ? 1 : 0;
     if (stem_x && name == "backbone.conv1b") {
@@ -723,12 +721,7 @@ struct Plan {
     a.w = m->blob + (split ? c.w16_off : c.w_off);
     a.w_tr = (split && c.w16t_off) ? m->blob + c.w16t_off : nullptr;
     a.tiles_x = (Wc + 15) / 16; a.tiles_y = (Hc + 15) / 16;
-    // Small grids (a frame or two at a time): a 64-channel-group launch would leave most CUs idle and each of its
-    // few workgroups is a long serial chain; 32-channel groups double the workgroups and halve their length.
-    // (a forced warp-specialised form — kp2d_set_option("wsm_min_items"), the parity tests — keeps its 64-channel groups)
-    const bool wsm_forced = m->wsm_min > 0 && (long)((Wc + 31) / 32) * ((Hc + 15) / 16) * B * (c.npad / 64) >= m->wsm_min;
-    if (split && c.npad >= 64 && m->small_grid_ng32 && !wsm_forced && s0.fmt == 0 && !a.wsm_force &&      // (S16P tensors: 64-channel groups)
-        (long)a.tiles_x * a.tiles_y * B * (c.npad / 64) < 256) {
+    if (split && s0.fmt == 0 && !a.wsm_force && use_ng32(B, Hc, Wc, c.npad, m->wsm_min)) {      // (S16P tensors: 64-channel groups)
       a.w = m->blob + c.w16n_off;
       a.ng32 = 1;
     }
@@ -742,7 +735,7 @@ struct Plan {
   }
   // score / loc / depth heads: 1-4 output channels as an HBM-bound dot-product kernel (exact fp32 in both modes)
   bool head_dot(const ConvPack& c, const ConvArgs& a) const {
-    return c.head() && a.store == ST_NCHW && a.in1.c == 0 && a.act != ACT_SOFTMAX_C && m->head_dot;
+    return c.head() && a.store == ST_NCHW && a.in1.c == 0 && a.act != ACT_SOFTMAX_C;
   }
   void head_dot_args(const ConvPack& c, ConvArgs& a) const {
     a.prec = 0;
@@ -793,8 +786,7 @@ struct Plan {
     if (!conv_args(n1, dense(ptr(in1), in1, in1.C, 0), none1, act1, ST_NCHW, out1, 0, 0, nullptr, 0, 0, c1.cout, Hc, Wc, a1)) return;
     // few frames only: at 64 frames the two launches overlap their tails and the pair is 0.4 % of the step slower
     // (21.16k vs 21.24k frames/s, three alternating runs); at one frame it saves a 4-us launch (0.273 -> 0.265 ms)
-    static const bool pair_env = !(getenv("KP2D_HEAD_PAIR") && getenv("KP2D_HEAD_PAIR")[0] == '0');      // (A/B knob)
-    const bool pair_on = pair_env && (long)((Wc + 15) / 16) * ((Hc + 3) / 4) * B < 1024;
+    const bool pair_on = (long)((Wc + 15) / 16) * ((Hc + 3) / 4) * B < 1024;
     if (!pair_on || m->profiling || !head_dot(c0, a0) || !head_dot(c1, a1) || c0.cout != 1 || c1.cout != 2) {
       conv(n0, in0, in0.C, 0, nullptr, act0, ST_NCHW, out0, 0, 0, nullptr, 0, 0, c0.cout, Hc, Wc);
       conv(n1, in1, in1.C, 0, nullptr, act1, ST_NCHW, out1, 0, 0, nullptr, 0, 0, c1.cout, Hc, Wc);
@@ -972,6 +964,7 @@ void build(Plan& P, const FwdOut& o, uint32_t flags) {
   const bool v3 = g.version == 3;
   const int lk = g.leaky_relu ? ACT_LEAKY : ACT_RELU;
   const int H = P.H, W = P.W, B = P.B;
+  const int cus = device_cu_count();      // (conv_policy.h: the persistent forms' grids, CUs / lanes)
 
   // ---- backbone (encoders.py:105-129) ----
   // Big grids: conv1a inside conv1b's launch (conv3x3_f16.hip STEM) — its output, the largest tensor of the forward after
@@ -980,7 +973,7 @@ void build(Plan& P, const FwdOut& o, uint32_t flags) {
   // The first layer in the split-fp16 arithmetic (RGB frames, 16 channels): one set of bits whether it runs fused, as its own
   // launch, or straight from uint8 frames — so a forward's results do not depend on the grid size that picks the form.
   const bool c1a_split = m->stem_fusion != 0 && m->precision == KP2D_PREC_F16X3 && g.in_channels == 3 && m->c1 == 16;
-  const bool stem = c1a_split && m->stem_fusion == 1 && !o.frames && m->c2 == 32 && g.downsample >= 2 && conv3x3_ws_would_run(B, H, W, m->ws_min) &&
+  const bool stem = c1a_split && m->stem_fusion == 1 && !o.frames && m->c2 == 32 && g.downsample >= 2 && ws_map_ok(B, H, W, m->ws_min) &&
                     !(m->tap_dst && m->tap_name == "backbone.conv1a");
   Act t1a = P.alloc(m->c1, H, W);      // (allocated either way: the workspace size must not depend on the input kind or on a tap)
   if (stem) P.stem_x = o.x;
@@ -1009,8 +1002,7 @@ void build(Plan& P, const FwdOut& o, uint32_t flags) {
   // the whole chain, because the layout has exactly one reader and two writers: S configs (16 -> 32 -> 32 -> 32 -> 64, two
   // pools), split-fp16 arithmetic, and a grid big enough for the persistent forms of both ends.
   const bool s16 = m->precision == KP2D_PREC_F16X3 && g.downsample == 2 && m->c1 == 16 && m->c2 == 32 && m->c3 == 32 && m->c4 == 64 &&
-                   m->s16_min >= 0 && conv3x3_ws_would_run(B, H, W, m->ws_min) &&
-                   conv3x3_s16_would_run(B, H / 2, W / 2, P.nlanes, m->s16_min, m->wsm_grid);
+                   ws_map_ok(B, H, W, m->ws_min) && s16_would_run(B, H / 2, W / 2, cus, P.nlanes, m->s16_min, m->wsm_grid);
   Act p1 = P.cbr("backbone.conv1b", t1a, nullptr, s16 ? ST_S16P_POOL : (g.downsample >= 2 ? ST_NHWC_POOL : ST_NHWC));
   P.release(t1a);
   Act t2a = P.cbr("backbone.conv2a", p1, nullptr, s16 ? ST_S16P : ST_NHWC);
@@ -1021,24 +1013,22 @@ void build(Plan& P, const FwdOut& o, uint32_t flags) {
   P.release(t2b);
   const bool only_enc = (flags & KP2D_FWD_ONLY_ENCODER) != 0;   // only_encoder(): skip every head but the VPR encoder
   // First CBR of every head in one launch ("heads.first", see describe()); first(name) hands out its channel slices.
-  static const bool merge_env = !(getenv("KP2D_MERGE_HEADS") && getenv("KP2D_MERGE_HEADS")[0] == '0');
   // Where a head's own launch would be a small grid (a frame or two per call) the five launches are five serial latencies
   // (0.42 -> 0.37 ms per frame).  On big grids the merged layer is ONE launch of the warp-specialised form with five times
   // the rounds (its start-up and drain paid once: conv family 333 -> 343 TFLOP/s at 64 x 240 x 320) against strided slice
   // reads in the five consumers: +0.1 ... +0.6 % at 64 frames, +1.4 % at 32, +0.9 % at 16, +0.6 % at 480 x 640, +0.9 % N
   // (profiles/r4_ab_merged_heads.txt); V3 (three parts), fp32 arithmetic and 30 x 40 head maps measured -0.2 ... -0.8 %
-  // and keep their own launches.  KP2D_MERGE_HEADS: 0 never, 2 always.
+  // and keep their own launches.
   const int Hc = H >> g.downsample, Wc = W >> g.downsample;      // the cell grid (backbone output)
-  const bool small_grid = (long)((Hc + 15) / 16) * ((Wc + 15) / 16) * P.B < 256;
-  static const bool merge_always = getenv("KP2D_MERGE_HEADS") && getenv("KP2D_MERGE_HEADS")[0] == '2';
+  const bool small_heads = small_grid(B, Hc, Wc, 1);
   // (round 5: 30 x 40 head maps too once the merged layer — five times the work items of one head's — runs on the
   // warp-specialised form: 64 frames of 120 x 160: five launches of 0.031 ms -> one of 0.102, +0.5 ... +2 % end to end)
   const int merged_groups = m->conv_index.count("heads.first") ? (m->convs[m->conv_index.at("heads.first")].npad / 64) : 0;
   const bool big_wsm = m->precision == KP2D_PREC_F16X3 && !v3 && m->wsm_min >= 0 &&
                        ((long)Hc * Wc >= 60 * 80 ||
                         ((long)Hc * Wc >= 30 * 40 && merged_groups >= 2 &&
-                         conv3x3_wsm_would_run(B, Hc, Wc, merged_groups, P.nlanes, m->wsm_min, m->wsm_grid, 2)));
-  const bool merged = merge_env && (small_grid || merge_always || big_wsm) && !only_enc && m->conv_index.count("heads.first");
+                         wsm_would_run(B, Hc, Wc, merged_groups, cus, P.nlanes, m->wsm_min, m->wsm_grid, 2)));
+  const bool merged = (small_heads || big_wsm) && !only_enc && m->conv_index.count("heads.first");
   // Big grids of the plain V2 S configuration: S16P is the layout of EVERY tensor a split-fp16 3x3 layer of the warp-specialised
   // form reads — conv3b's two outputs, conv4a / 4b, the merged first layer's desc / seg / vlad slices, both pixel-shuffled
   // tensors, convs.5, convlad2 — so those layers' staging waves only issue LDS-DMA copies (conv3x3_wsm.hip IN16).  fp32 NHWC
@@ -1046,14 +1036,13 @@ void build(Plan& P, const FwdOut& o, uint32_t flags) {
   // and convs.2 / .3 (30 x 40 maps: general kernels), confAa's and convs.7's outputs (confBb / convs.8, planar outputs),
   // convlad3's (NetVLAD).  Same values bit for bit (a consumer multiplies the halves its own staging would have produced).
   // Decided once, on the form running for the smallest converted layer (conv4a); a tap keeps its layer readable either way.
-  static const bool s16all_env = !(getenv("KP2D_S16ALL") && getenv("KP2D_S16ALL")[0] == '0');      // (A/B knob)
   const int Hq = H / 4, Wq = W / 4;
-  const bool s16_all = s16 && s16all_env && m->s16_all && !v3 && !only_enc && !g.use_attention && !g.depth &&
+  const bool s16_all = s16 && m->s16_all && !v3 && !only_enc && !g.use_attention && !g.depth &&
                        g.upscale_method != KP2D_UP_CONVTRANSPOSE && m->c5 == 64 && m->d1 == 128 && g.encoder_dim == 64 &&
                        m->wsm_min >= 0 && m->wsm_tr == 0 && merged &&
                        Wq / 2 >= 32 &&      // (convs.4 writes its pixel-shuffled S16P output from a W / 8 map: the form's least width
                        (long)((Wq / 2 + 31) / 32) * ((Hq / 2 + 15) / 16) * B * 2 >= 8 &&      //  and its least grid, eight work items)
-                       conv3x3_wsm_would_run(B, Hq, Wq, 1, P.nlanes, m->wsm_min, m->wsm_grid, 1);
+                       wsm_would_run(B, Hq, Wq, 1, cus, P.nlanes, m->wsm_min, m->wsm_grid, 1);
   Act xp{};
   Act skip = P.cbr("backbone.conv3b", t3a, nullptr, s16_all ? ST_S16P_BOTH : ST_NHWC_BOTH, &xp);   // downsample >= 1 always
   P.release(t3a);
@@ -1065,11 +1054,10 @@ void build(Plan& P, const FwdOut& o, uint32_t flags) {
   if (xb.H != Hc || xb.W != Wc) { P.rc = fail(KP2D_ERR_ARG, "plan: cell grid %dx%d, expected %dx%d", xb.H, xb.W, Hc, Wc); return; }
 
   // the two planar outputs behind a 64-channel S16P tensor (conv3x3_s16.hip's planar form: cout <= 32 plain logits)
-  static const bool planar_env = !(getenv("KP2D_S16PLANAR") && getenv("KP2D_S16PLANAR")[0] == '0');      // (A/B knob)
   // (not the class logits when the forward also writes the dense class map: the argmax over channels that sit in 32 different
   // lanes — DPP rotations per pixel — made that layer 0.147 -> 0.189 ms; the general kernel finds it in its LDS tile)
   auto s16_planar = [&](int cout, bool with_ids = false) {
-    return s16_all && planar_env && !with_ids && cout <= 32 && m->c4 == 64 && m->c5 == 64 && !(W2 & 3);
+    return s16_all && !with_ids && cout <= 32 && m->c4 == 64 && m->c5 == 64 && !(W2 & 3);
   };
   Act mx{}, mxs{};
   int mx_split = 1 << 30;      // first channel of the merged layer kept in the S16P tensor mxs (s16_all: behind score | loc)
@@ -1153,7 +1141,7 @@ void build(Plan& P, const FwdOut& o, uint32_t flags) {
   // 17 launches -> 12 behind the merged first layer.  Same kernels, same arithmetic, per layer.
   // (a dry run sizes the workspace for whichever schedule keeps more tensors alive — P.no_levels picks; profiles and taps
   // take the layers one launch at a time)
-  const bool levels = merged && small_grid && !v3 && !g.use_attention && !g.depth && g.upscale_method != KP2D_UP_CONVTRANSPOSE &&
+  const bool levels = merged && small_heads && !v3 && !g.use_attention && !g.depth && g.upscale_method != KP2D_UP_CONVTRANSPOSE &&
                       m->precision == KP2D_PREC_F16X3 && m->multi_launch && !P.no_levels && !s16_all &&
                       (P.dry || (!m->profiling && !m->tap_dst));
   if (levels) {
@@ -1370,7 +1358,7 @@ int validate_shape(const kp2d_model* m, int B, int H, int W) {
   return KP2D_OK;
 }
 
-size_t plan_bytes(kp2d_model* m, int Bc, int H, int W);
+size_t plan_bytes(kp2d_model* m, int Bc, int H, int W, int lanes);
 
 // Frames per internal sub-batch.  Measured on MI355X (profiles/r1_*): the path is compute-bound, so bigger
 // launches win (64 frames at once: 5.4k frames/s vs 3.7k with 10-frame sub-batches that keep intermediates
@@ -1378,34 +1366,35 @@ size_t plan_bytes(kp2d_model* m, int Bc, int H, int W);
 // choice therefore only caps the workspace (4 GiB), it does not chase cache residency.
 int auto_chunk(const kp2d_model* m, int B, int H, int W) {
   if (m->chunk_frames > 0) return std::min(B, m->chunk_frames);
-  const size_t per_frame = plan_bytes(const_cast<kp2d_model*>(m), 1, H, W);
+  const size_t per_frame = plan_bytes(const_cast<kp2d_model*>(m), 1, H, W, 1);
   if (per_frame == 0) return 1;
   const size_t cap = (size_t)4 << 30;
   return (int)std::max<size_t>(1, std::min<size_t>((size_t)B, cap / per_frame));
 }
 
-size_t plan_bytes_uncached(kp2d_model* m, int Bc, int H, int W);
+size_t plan_bytes_uncached(kp2d_model* m, int Bc, int H, int W, int lanes);
 
-// dry-run planning costs ~0.1 ms of host time; the result only depends on (frames, H, W), so it is memoised
-size_t plan_bytes(kp2d_model* m, int Bc, int H, int W) {
-  const uint64_t key = ((uint64_t)Bc << 40) ^ ((uint64_t)H << 20) ^ (uint64_t)W;
+// dry-run planning costs ~0.1 ms of host time; the result only depends on (frames, H, W, lanes) — the lane count sizes the
+// persistent forms' grids, which fix activation layouts (conv_policy.h) — so it is memoised
+size_t plan_bytes(kp2d_model* m, int Bc, int H, int W, int lanes) {
+  const uint64_t key = ((uint64_t)lanes << 60) ^ ((uint64_t)Bc << 40) ^ ((uint64_t)H << 20) ^ (uint64_t)W;
   auto it = m->plan_cache.find(key);
   if (it != m->plan_cache.end()) return it->second;
-  const size_t v = plan_bytes_uncached(m, Bc, H, W);
+  const size_t v = plan_bytes_uncached(m, Bc, H, W, lanes);
   m->plan_cache[key] = v;
   return v;
 }
 
-size_t plan_bytes_uncached(kp2d_model* m, int Bc, int H, int W) {
+size_t plan_bytes_uncached(kp2d_model* m, int Bc, int H, int W, int lanes) {
   Plan P{};
-  P.m = m; P.stream = nullptr; P.ws = nullptr; P.dry = true; P.B = Bc; P.H = H; P.W = W;
+  P.m = m; P.stream = nullptr; P.ws = nullptr; P.dry = true; P.B = Bc; P.H = H; P.W = W; P.nlanes = lanes;
   P.arena.reset((size_t)1 << 46);
   FwdOut o{};
   build(P, o, 0);
   if (P.rc != KP2D_OK) return 0;
   // the level-by-level schedule of small grids and the head-by-head one keep different tensors alive: room for either
   Plan Q{};
-  Q.m = m; Q.stream = nullptr; Q.ws = nullptr; Q.dry = true; Q.B = Bc; Q.H = H; Q.W = W; Q.no_levels = true;
+  Q.m = m; Q.stream = nullptr; Q.ws = nullptr; Q.dry = true; Q.B = Bc; Q.H = H; Q.W = W; Q.nlanes = lanes; Q.no_levels = true;
   Q.arena.reset((size_t)1 << 46);
   build(Q, o, 0);
   return Q.rc == KP2D_OK ? std::max(P.arena.high, Q.arena.high) : 0;
@@ -1453,6 +1442,15 @@ int kp2d_create(const kp2d_config* cfg, kp2d_model** out) {
   if (nlanes) m->lanes = std::max(1, std::min(8, atoi(nlanes)));
   m->lanes_default = m->lanes;
   if (getenv("KP2D_SIDE") && getenv("KP2D_SIDE")[0] == '0') m->side_overlap = false;      // (A/B knob)
+  // A/B switches of the conv path: initial values of their kp2d_set_option equivalents (conv_policy.h reads only options)
+  long v = 0;
+  auto env = [&v](const char* name) { const char* e = getenv(name); if (e && *e) v = atol(e); return e && *e; };
+  if (env("KP2D_WSM") && v >= 0) m->wsm_min = v == 0 ? -1 : (int)std::min(v, 0x7fffffffL);
+  if (env("KP2D_WSM_GRID") && v > 0) m->wsm_grid = (int)std::min(v, 65536L);
+  if (env("KP2D_WSM_TR") && v >= 0 && v <= 2) m->wsm_tr = (int)v;
+  if (env("KP2D_S16") && v == 0) m->s16_min = -1;
+  if (env("KP2D_S16ALL") && v == 0) m->s16_all = false;
+  if (env("KP2D_MULTI") && v == 0) m->multi_launch = false;
   *out = m;
   return KP2D_OK;
 }
@@ -1529,13 +1527,15 @@ int kp2d_import_packed(kp2d_model* m, const void* dev_src, void* stream) {
 }
 
 // Sub-batch schedule shared by kp2d_workspace_bytes and kp2d_forward: `lanes` concurrent streams, each working
-// through ceil(nchunks / lanes) sub-batches of `chunk` frames in its own slice of the workspace.
-static void schedule(const kp2d_model* m, int B, int H, int W, int* lanes, int* chunk) {
+// through ceil(nchunks / lanes) sub-batches of `chunk` frames in its own slice of the workspace.  Returns the size of a
+// slice: the plan of one sub-batch with the lanes that actually run side by side (fewer when there are fewer sub-batches).
+static size_t schedule(kp2d_model* m, int B, int H, int W, int* lanes, int* chunk) {
   int nl = m->profiling ? 1 : std::max(1, m->lanes);
   nl = std::min(nl, B);
-  int c = std::min(auto_chunk(m, B, H, W), (B + nl - 1) / nl);
+  int c = std::max(1, std::min(auto_chunk(m, B, H, W), (B + nl - 1) / nl));
   *lanes = nl;
-  *chunk = std::max(1, c);
+  *chunk = c;
+  return align_up(plan_bytes(m, c, H, W, std::min(nl, (B + c - 1) / c)));
 }
 
 size_t kp2d_vlad_dim(const kp2d_model* m, int H, int W) {
@@ -1553,14 +1553,12 @@ size_t kp2d_workspace_bytes(const kp2d_model* m, int B, int H, int W) {
   const bool prof = mm->profiling;
   mm->profiling = false;
   int nl, chunk;
-  schedule(m, B, H, W, &nl, &chunk);
-  mm->profiling = prof;
-  const size_t per = align_up(plan_bytes(mm, chunk, H, W));
-  int nl1, chunk1;
+  const size_t per = schedule(mm, B, H, W, &nl, &chunk);
   mm->profiling = true;
-  schedule(m, B, H, W, &nl1, &chunk1);
+  int nl1, chunk1;
+  const size_t per1 = schedule(mm, B, H, W, &nl1, &chunk1);
   mm->profiling = prof;
-  return std::max(per * nl, align_up(plan_bytes(mm, chunk1, H, W)));
+  return std::max(per * nl, per1);
 }
 
 static int forward_impl(kp2d_model* m, const float* x, const uint8_t* frames, int Hs, int Ws, int B, int H, int W,
@@ -1580,8 +1578,7 @@ static int forward_impl(kp2d_model* m, const float* x, const uint8_t* frames, in
   if (m->seg_ids_dst && !only_enc && m->seg_ids_cap < (size_t)B * (2 * (H >> m->cfg.downsample)) * (2 * (W >> m->cfg.downsample)))
     return fail(KP2D_ERR_ARG, "kp2d_set_seg_ids: buffer of %zu ids is too small for this forward", m->seg_ids_cap);
   int nl, chunk;
-  schedule(m, B, H, W, &nl, &chunk);
-  const size_t per = align_up(plan_bytes(m, chunk, H, W));
+  const size_t per = schedule(m, B, H, W, &nl, &chunk);
   if (per == 0) return KP2D_ERR_WORKSPACE;
   if (workspace_bytes < per * nl) return fail(KP2D_ERR_WORKSPACE, "workspace %zu B < required %zu B", workspace_bytes, per * nl);
   const kp2d_config& g = m->cfg;
@@ -1614,7 +1611,7 @@ static int forward_impl(kp2d_model* m, const float* x, const uint8_t* frames, in
     P.m = m; P.stream = lane == 0 ? caller : m->lane_streams[lane - 1];
     P.ws = (char*)workspace + (size_t)lane * per; P.dry = false;
     P.B = std::min(chunk, B - b0); P.H = H; P.W = W; P.b0 = b0;
-    P.nlanes = std::min(nl, (B + chunk - 1) / chunk);
+    P.nlanes = std::min(nl, (B + chunk - 1) / chunk);      // (as schedule() sized the slice)
     P.arena.reset(per);
     FwdOut o{};
     o.x = x ? x + (size_t)b0 * g.in_channels * H * W : nullptr;

@@ -3,74 +3,9 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include "conv_policy.h"
 
 namespace kp2d {
-
-// ---- activation / epilogue selectors -------------------------------------------------------
-enum Act : int {
-  ACT_NONE = 0,
-  ACT_LEAKY = 1,           // LeakyReLU(0.01)       modules/base.py:33
-  ACT_RELU = 2,            // ReLU (to_mcu configs) modules/base.py:35
-  ACT_SIGMOID = 3,         // score head            models/kp2dtiny.py:574
-  ACT_TANH = 4,            // loc head              models/kp2dtiny.py:575
-  ACT_SIGMOID0_TANH = 5,   // V3 fused score/loc: ch0 sigmoid, ch1..2 tanh  models/kp2dtiny.py:927-935
-  ACT_SOFTMAX_C = 6,       // V3 eval: Softmax2d over classes                models/kp2dtiny.py:942-943
-  ACT_GELU = 7,            // exact-erf GELU inside MixFeedForward           modules/segformer.py:185
-};
-
-enum Store : int {
-  ST_NHWC = 0,             // out0[pixel][os0] (+oo0), full resolution
-  ST_NHWC_POOL = 1,        // out1 = MaxPool2d(2,2) of the activation only
-  ST_NHWC_BOTH = 2,        // out0 full-res AND out1 pooled (conv3b: skip + x)
-  ST_SHUFFLE = 3,          // PixelShuffle(2) folded into the store: out0 is the 2H x 2W NHWC tensor
-  ST_NCHW = 4,             // API-facing planar output; channels [0,nsplit) -> out0, [nsplit,cout) -> out1
-  ST_S16P = 5,             // out0 is an S16P tensor (below), full resolution
-  ST_S16P_POOL = 6,        // out1 = MaxPool2d(2,2) of the activation as an S16P tensor (conv1b)
-  ST_S16P_BOTH = 7,        // out0 full-res AND out1 pooled, both S16P tensors (conv3b: skip + x)
-  ST_S16P_SHUFFLE = 8,     // PixelShuffle(2) folded into the store, out0 the 2H x 2W S16P tensor (cout / 4 a multiple of 32)
-  ST_MIX16 = 9,            // 64-channel groups below channel `nsplit`: fp32 NHWC into out0 (os0 channels); from `nsplit` on: the
-                           // S16P tensor out1 (os1 channels, its chunk 0 = channel nsplit) — the heads' merged first layer, whose
-                           // score / location slices are read by the fp32 dot-product kernels and the rest by split-fp16 convs
-};
-// S16P ("split, planar rows"): an activation kept as the fp16 halves the split-fp16 kernels multiply, x = hi + lo with
-// hi = fp16(x), lo = fp16(x - hi) — per frame [C / 16 chunks][H][plane: hi | lo][W][16 halves], the same bytes as fp32 NHWC.
-// A tile row of one plane is contiguous, so the consumer copies its LDS operand image straight from HBM (conv3x3_s16.hip).
-// Only between layers of one forward (workspace tensors); C a multiple of 16.  Readers: conv3x3_s16.hip (32 input channels, the
-// layer's weights resident in LDS) and conv3x3_wsm.hip's IN16 form (any whole number of chunks, one or two S16P sources).
-
-// One 3x3 / stride 1 / pad 1 (taps = 9) or 1x1 (taps = 1) convolution over an NHWC activation that may be
-// the channel-concat of two tensors (torch.cat([up, skip], 1): heads.py:99, segmentation.py:141,149).
-// A source is addressed as ptr + b*bs + y*rs + x*ps + o + c, so strided views work too: the 2x2 stride-2
-// to_kv conv (modules/segformer.py:93-95) is a 1x1 conv over two row-views of the full-resolution tensor.
-struct ConvSrc { const float* p; int c, o; long bs, rs, ps; int fmt; };   // channels taken, first channel, strides (floats); fmt 1: an S16P tensor (bs only)
-struct ConvArgs {
-  ConvSrc in0, in1;
-  int taps;                           // 9 or 1
-  int prec;                           // 0: exact fp32 MFMA, 1: split-fp16 3xMFMA (weights packed as hi|lo halves)
-  const float* w;                     // packed [group][cin_pad/KC][taps][ng][KC]
-  const float* scale;                 // [npad]  BN: gamma/sqrt(var+eps); bias conv: 1
-  const float* shift;                 // [npad]  BN: beta - mean*scale;   bias conv: bias
-  float* out0; int os0, oo0;
-  float* out1; int os1, oo1;
-  int B, H, W;                        // conv resolution
-  int cin, cout, npad;
-  int act, store, nsplit;
-  int tiles_x, tiles_y;
-  int ng32;                           // 1: w holds 32-channel groups although npad >= 64 (small grids)
-  int wsm_min;                        // least (tile, group) work items for the warp-specialised multi-chunk form; 0: automatic (KP2D_WSM, else one per workgroup); < 0: never
-  const float* w_tr;                  // the 64-channel-group pack with the taps transposed (dy <-> dx), nullptr: none (conv3x3_wsm.hip: transposed tiles)
-  int wsm_tr;                         // conv3x3_wsm.hip: tiles walk the map transposed (tile rows = map columns).  In: 0 never, 1 always, 2 where cheaper; the launcher hands the kernel its decision (0 / 1)
-  int wsm_lanes;                      // stream lanes launching side by side (the form takes CUs / lanes workgroups)
-  long long* ids_out;                 // ST_NCHW, one channel group: also write argmax over the stored channels per pixel, [B][H][W] int64 (nullptr: no)
-  int ws_min;                         // least tiles for the warp-specialised conv1b form (0: 1024)
-  int wsm_grid;                       // most workgroups of that form per launch; 0: KP2D_WSM_GRID or one per CU
-  // conv1b's warp-specialised form with conv1a computed by its staging waves (conv3x3_f16.hip STEM): the frames [B,3,H,W] and
-  // conv1a's weights [27][16] / folded BatchNorm; in0 is then unused.  nullptr: conv1a is its own launch
-  const float* stem_x; const float* stem_w; const float* stem_scale; const float* stem_shift; const float* stem_wscale; int stem_act;   // stem_wscale: device pointer to 2^e
-  int s16_min;                        // conv3x3_s16.hip: least work items for the form (0: automatic, three rounds per workgroup)
-  int wsm_force;                      // the plan fixed this layer's tensor layouts on conv3x3_wsm.hip running it (S16P in or out): no item-count policy
-  int dbg;                            // timing ablations only (KP2D_DBG): 1 skip the epilogue, 2 skip LDS commit, 4 skip global loads, 8 skip MFMA, 64 skip only the epilogue's global stores
-};
 
 struct Conv1aArgs {                   // backbone.conv1a: NCHW frame in -> NHWC out, Cin = 3 (RGB) or 1 (use_color=False)
   const float* x;                     // [B,cin,H,W]
@@ -91,21 +26,14 @@ int launch_conv1a_u8(const Conv1aArgs& a, const unsigned char* frames, int Hs, i
 int launch_conv1a_mfma(const Conv1aArgs& a, const float* wscale_dev, const unsigned char* frames, int Hs, int Ws, hipStream_t s);
 int launch_head3x3_pair(const ConvArgs& a0, const ConvArgs& a1, hipStream_t s);   // a 1-channel and a 2-channel head, one launch
 int launch_head3x3(const ConvArgs& a, hipStream_t s);         // head3x3.hip: taps = 9, cout <= 4, planar outputs (exact fp32 dot products)
-int launch_conv3x3_f16x3(const ConvArgs& a, hipStream_t s);   // conv3x3_f16.hip: taps = 9, prec = 1 (16x16x32 MFMA)
+int launch_conv3x3_f16x3(const ConvArgs& a, hipStream_t s);   // conv3x3_f16.hip: taps = 9, prec = 1, the form conv_policy.h chooses
 // 2-4 independent small-grid layers as one launch; -1000: not all of them are layers of the single-frame form
 int launch_conv3x3_f16x3_multi(const ConvArgs* list, int n, hipStream_t s);
-// conv3x3_wsm.hip: the same layers, 64-channel groups, warp-specialised and persistent; -1000 = not eligible / fewer than min_items work items
-int launch_conv3x3_f16x3_wsm(const ConvArgs& a, hipStream_t s, int n_item);   // n_item: 64 (64-channel groups) or 32 (32-channel layers)
-// conv3x3_s16.hip: 32-input-channel layers whose input is an S16P tensor (in0.fmt == 1); -1000: in0 is not S16P
-int launch_conv3x3_f16x3_s16(const ConvArgs& a, hipStream_t s);
-// would that form run for a B x H x W map (the plan decides the activation layout of conv1b .. conv3a's outputs by it)
-bool conv3x3_s16_would_run(int B, int H, int W, int lanes, int min_items, int grid_opt);
-// would the warp-specialised conv1b form (conv3x3_f16.hip, the only producer of a pooled S16P tensor) run
-bool conv3x3_ws_would_run(int B, int H, int W, int ws_min);
+// conv3x3_wsm.hip / conv3x3_s16.hip: the persistent forms, launched as conv_policy.h chose them
+int launch_conv3x3_f16x3_wsm(const ConvArgs& a, const ConvChoice& c, hipStream_t s);
+int launch_conv3x3_f16x3_s16(const ConvArgs& a, const ConvChoice& c, hipStream_t s);
 // kp2d_set_tap on an S16P tensor: channels [c0, c0 + C) of a Ct-channel tensor -> planar fp32
 int launch_s16p_to_nchw(const float* in, float* out, int B, int C, int H, int W, int Ct, int c0, hipStream_t s);
-// would conv3x3_wsm.hip's automatic policy take a 64-channel-group layer of `groups` groups on a B x H x W map
-bool conv3x3_wsm_would_run(int B, int H, int W, int groups, int lanes, int wsm_min, int grid_opt, int full_rounds);
 
 // ---- NetVLAD (modules/aggregators/netvlad.py:79-106) ---------------------------------------
 struct VladArgs {

@@ -1572,6 +1572,32 @@ def test_plan_sizes_follow_the_arithmetic_mode_and_options():
         assert eng.lib.kp2d_set_option(eng.handle, b"lanes", 9) != 0
 
 
+@pytest.mark.parametrize("lanes", [1, 2])
+@pytest.mark.parametrize("B,H,W", [(16, 120, 160), (32, 120, 160), (64, 120, 160), (1, 240, 320), (8, 240, 320),
+                                   (16, 240, 320), (32, 240, 320), (1, 480, 640), (4, 480, 640)])
+def test_plan_sizes_follow_the_arithmetic_mode_and_options_per_lane_count(lanes, B, H, W):
+    """kp2d_workspace_bytes sizes each lane's slice with the lane count the forward then runs with: the persistent forms
+    take CUs / lanes workgroups, and whether they run fixes the activation layouts (S16P through the backbone, S16P
+    everywhere, merged heads).  Batch sizes on both sides of those thresholds: each forward runs in a workspace of exactly
+    the size asked for (a plan larger than its slice fails with "workspace exhausted"), and equals bit for bit the same
+    forward in a workspace twice that size."""
+    model, _ = product_model("S", False, 28)
+    x = torch.from_numpy(synthetic_frames(B, H, W, seed=5)).to(DEV)
+    with torch.no_grad():
+        model(x[:1])
+        eng = model._engine
+        assert eng.lib.kp2d_set_option(eng.handle, b"lanes", lanes) == 0
+        need = eng.lib.kp2d_workspace_bytes(eng.handle, B, H, W)
+        assert need > 0
+        with eng.using_workspace(torch.empty(2 * need, dtype=torch.uint8, device=DEV)):
+            want = {k: v.clone() for k, v in model(x).items()}
+        with eng.using_workspace(torch.empty(need, dtype=torch.uint8, device=DEV)):
+            got = {k: v.clone() for k, v in model(x).items()}
+        assert eng.lib.kp2d_set_option(eng.handle, b"lanes", 0) == 0
+    for k in want:
+        assert torch.equal(want[k], got[k]), k
+
+
 @pytest.mark.parametrize("slots", [2, 3])
 def test_batch_stream_equals_the_plain_loop(slots):
     """pipeline.BatchStream (several batches in flight on alternating HIP streams, one engine lane per forward, a
