@@ -222,7 +222,13 @@ int kp2d_profile_get(kp2d_model* m, int index, const char** layer, const char** 
  *   KP2D_PREC_FP32   exact fp32 on v_mfma_f32_32x32x2_f32 (bit-for-bit an fp32 fma chain)
  *   KP2D_PREC_F16X3  split fp16: x*w = xh*wh + xh*wl + xl*wh on v_mfma_f32_16x16x32_f16 (3x3 convolutions; the 1x1
  *                    convolutions and the attention kernel use v_mfma_f32_32x32x16_f16), fp32 accumulate, fp32-grade error
- *                    (default; see DESIGN.md "Numerics").  Both weight packs are resident; switching is free. */
+ *                    (default; see DESIGN.md "Numerics").  Both weight packs are resident; switching is free.
+ *                    Range: every layer's output stays inside the float64 error bound of tests/layer_ref.py (fp32
+ *                    accumulation plus the split's 2^-22 relative / 2^-25 absolute representation error) for input
+ *                    activations of any magnitude below 2^16, fp16 subnormals and zero included (checked per layer down
+ *                    to 2^-24 of the layer's normal range by tests/test_gpu_layer_fp64.py).  From 65504 to 131008 the hi
+ *                    half saturates and the lo half carries the rest in fp16 precision (no longer fp32-grade); values
+ *                    beyond +-131008 saturate. */
 #define KP2D_PREC_FP32 0
 #define KP2D_PREC_F16X3 1
 int kp2d_set_precision(kp2d_model* m, int mode);
