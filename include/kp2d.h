@@ -284,6 +284,47 @@ int kp2d_set_chunk_frames(kp2d_model* m, int frames);
  * family ("conv3x3_f16x3<wsm>", "conv3x3_f16x3<2,1,16>", ...). */
 int kp2d_set_option(kp2d_model* m, const char* key, long value);
 
+/* ---- Place recognition: flat squared-L2 top-k over global descriptors (nano-vs-slam_amd/csrc/vpr.hip) ----------
+ * Replaces the faiss.IndexFlatL2 search of the reference's evaluate_global_descriptor
+ * (src/evaluation/global_descriptor.py:55-60): for every query row the k nearest database rows by exact brute-force
+ * squared L2 distance.  Stateless like the rest of the ABI: caller-owned device buffers, the caller's stream, no
+ * synchronisation.  The Q x N distance matrix is never written.
+ *   dim: dim % 16 == 0 and 16 <= dim <= 16384 (every shipped descriptor: 768 ... 8192), else KP2D_ERR_UNSUPPORTED.
+ *   kp2d_vpr_pack: the database rows x [n,dim] fp32 -> packed [kp2d_vpr_packed_bytes(n, dim)] bytes.  Row r occupies
+ *     bytes [r (4 dim + 16), (r + 1)(4 dim + 16)) and depends on row r alone, so a database grows by packing only the
+ *     new rows at its end.  Holds |x|^2, the split-fp16 form of the row and its range-guard bit.
+ *   kp2d_vpr_search: db [ndb,dim] fp32 and packed_db (kp2d_vpr_pack of the same rows; both precisions read its row
+ *     norms), queries q [nq,dim] fp32 -> dist [nq,k] float, idx [nq,k] int64.
+ *     dist holds SQUARED L2 distances (what IndexFlatL2.search returns), ascending, equal distances by lower row; equal
+ *     rows therefore come out in ascending index order and a query equal to a row gets distance 0.  Slots past the rows
+ *     available get idx = -1 and dist = FLT_MAX (faiss's flat-index padding).
+ *     limit [nq] int64 or NULL: query i only sees rows [0, limit[i]) (<= 0: none) — e.g. loop-closure candidates of a
+ *     whole trajectory in one call with limit[t] = t - W.
+ *     k in [1, 1024] (k <= 32 is the fast path: the merge of database slices then takes 64 or more slices per pass).
+ *     scratch: kp2d_vpr_scratch_bytes(nq, ndb, dim, k) bytes; q, db, packed_db and scratch 16-byte aligned.
+ *     Bad arguments: KP2D_ERR_ARG.
+ *   Accuracy.  Candidates are ranked by key = |d|^2 - 2 q.d; the k finalists are then re-scored directly as
+ *     sum (q - d)^2 in fp32, so a returned distance is within 32 u d64 + 2 u d64 of float64 (u = 2^-24; d64 the float64
+ *     distance of the same fp32 rows).  Default (flags = 0): the key's q.d in split fp16, q = 2^-s (qh + ql) with a
+ *     power of two s per row putting max|q| 2^s in [2^14, 2^15), three fp16 products per pair on the matrix cores,
+ *     fp32 accumulation: |key error| <= 2 (32 u + 3 * 2^-22) sum|q_i d_i| + 32 u |d|^2, plus the subnormal floor
+ *     2^-38 (max|q| sum|d_i| + max|d| sum|q_i|) (tests/test_vpr_cpu.py).  A row can be missing from the answer only if
+ *     its distance lies within twice that bound of the k-th distance.
+ *     flags & KP2D_VPR_FP32: q.d from exact fp32 products (v_mfma_f32_32x32x2_f32), key error <= 2 * 32 u sum|q_i d_i|
+ *     + 32 u |d|^2.
+ *     Range guard: a database row with a non-finite element or with max|d| outside [2^-40, 2^40) makes its 128-row
+ *     block of the database (rows [128 b, 128 b + 128)) take the fp32 products for every query; rows in range keep
+ *     the split's bound for any magnitude in between (the scale is per row), unnormalised GeM descriptors included.
+ *   Determinism: a query's result is bit-identical whatever nq is, whichever other queries share the call and however
+ *     the database is sliced over workgroups; packing rows in several calls gives the bytes of one call. */
+#define KP2D_VPR_FP32 1u
+size_t kp2d_vpr_packed_bytes(int64_t n, int dim);
+int kp2d_vpr_pack(const float* x, int64_t n, int dim, void* packed, void* stream);
+size_t kp2d_vpr_scratch_bytes(int nq, int64_t ndb, int dim, int k);
+int kp2d_vpr_search(const void* packed_db, const float* db, int64_t ndb, int dim, const float* q, int nq,
+                    const int64_t* limit, int k, uint32_t flags, float* dist, int64_t* idx, void* scratch,
+                    size_t scratch_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1966,4 +1966,54 @@ int kp2d_set_chunk_frames(kp2d_model* m, int frames) {
   return KP2D_OK;
 }
 
+// ---- place recognition (vpr.hip) ----
+static int vpr_dim_check(int dim) {
+  if (dim < 16 || dim > 16384 || dim % 16) return fail(KP2D_ERR_UNSUPPORTED, "vpr: descriptor dim %d (needs dim %% 16 == 0, 16 <= dim <= 16384)", dim);
+  return KP2D_OK;
+}
+size_t kp2d_vpr_packed_bytes(int64_t n, int dim) {
+  if (n < 0 || dim < 16 || dim > 16384 || dim % 16) return 0;
+  return (size_t)n * vpr_row_bytes(dim);
+}
+
+int kp2d_vpr_pack(const float* x, int64_t n, int dim, void* packed, void* stream) {
+  if (int e = vpr_dim_check(dim)) return e;
+  if (n < 0 || n > INT32_MAX) return fail(KP2D_ERR_ARG, "vpr_pack: row count %lld", (long long)n);
+  if (n == 0) return KP2D_OK;
+  if (!x || !packed) return fail(KP2D_ERR_ARG, "null argument");
+  if ((uintptr_t)x % 16 || (uintptr_t)packed % 16) return fail(KP2D_ERR_ARG, "vpr_pack: x and packed must be 16-byte aligned");
+  DeviceGuard guard(x, (hipStream_t)stream);
+  if (int e = launch_vpr_pack(x, n, dim, packed, (hipStream_t)stream)) return fail(KP2D_ERR_HIP, "vpr_pack kernel: %d", e);
+  return KP2D_OK;
+}
+
+size_t kp2d_vpr_scratch_bytes(int nq, int64_t ndb, int dim, int k) {
+  if (nq < 1 || ndb < 0 || ndb > INT32_MAX || dim < 16 || dim > 16384 || dim % 16 || k < 1 || k > 1024) return 0;
+  return vpr_plan(nq, ndb, dim, k).total;
+}
+
+int kp2d_vpr_search(const void* packed_db, const float* db, int64_t ndb, int dim, const float* q, int nq,
+                    const int64_t* limit, int k, uint32_t flags, float* dist, int64_t* idx, void* scratch,
+                    size_t scratch_bytes, void* stream) {
+  if (int e = vpr_dim_check(dim)) return e;
+  if (k < 1 || k > 1024) return fail(KP2D_ERR_ARG, "vpr_search: k = %d outside [1, 1024]", k);
+  if (nq < 0 || ndb < 0) return fail(KP2D_ERR_ARG, "vpr_search: negative size");
+  if (ndb > INT32_MAX) return fail(KP2D_ERR_UNSUPPORTED, "vpr_search: more than 2^31 - 1 database rows");
+  if (flags & ~(uint32_t)KP2D_VPR_FP32) return fail(KP2D_ERR_ARG, "unknown vpr flags 0x%x", flags);
+  if (nq == 0) return KP2D_OK;
+  if (!q || !dist || !idx || !scratch || (ndb > 0 && (!packed_db || !db))) return fail(KP2D_ERR_ARG, "null argument");
+  if ((uintptr_t)q % 16 || (uintptr_t)db % 16 || (uintptr_t)packed_db % 16 || (uintptr_t)scratch % 16)
+    return fail(KP2D_ERR_ARG, "vpr_search: q, db, packed_db and scratch must be 16-byte aligned");
+  const size_t need = kp2d_vpr_scratch_bytes(nq, ndb, dim, k);
+  if (scratch_bytes < need) return fail(KP2D_ERR_WORKSPACE, "vpr scratch %zu B < required %zu B (kp2d_vpr_scratch_bytes)", scratch_bytes, need);
+  DeviceGuard guard(q, (hipStream_t)stream);
+  VprSearchArgs a{};
+  a.dbp = reinterpret_cast<const unsigned char*>(packed_db);
+  a.db = db; a.q = q; a.limit = limit; a.ndb = ndb; a.dim = dim; a.nq = nq; a.k = k;
+  a.fp32 = (flags & KP2D_VPR_FP32) ? 1 : 0;
+  if (int e = launch_vpr_search(a, reinterpret_cast<unsigned char*>(scratch), dist, idx, (hipStream_t)stream))
+    return fail(KP2D_ERR_HIP, "vpr_search kernels: %d", e);
+  return KP2D_OK;
+}
+
 }  // extern "C"

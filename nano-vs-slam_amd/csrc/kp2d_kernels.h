@@ -217,6 +217,23 @@ struct TopkPairsArgs {   // at most kcap matched pairs per frame pair, best firs
 int launch_match_topk_pairs(const TopkPairsArgs& a, hipStream_t s);
 int launch_match(const MatchArgs& a, hipStream_t s);
 
+// ---- vpr.hip: flat squared-L2 top-k over global descriptors (kp2d_vpr_*) ----------------------
+struct VprSearchArgs {
+  const unsigned char* dbp;        // packed database rows (kp2d_vpr_pack: 4 dim + 16 bytes each)
+  const float* db;                 // the same rows in fp32 [ndb, dim]
+  const unsigned char* qp;         // packed queries (scratch; set by launch_vpr_search)
+  const float* q;                  // [nq, dim]
+  const int64_t* limit;            // [nq] or null
+  int64_t ndb;
+  int dim, nq, k, fp32;
+  unsigned long long* codes;       // per-slice lists (scratch; set by launch_vpr_search)
+};
+struct VprPlan { int nz, G; size_t off_q, off_a, off_b, total; };   // database slices, merge fan-in, scratch layout
+VprPlan vpr_plan(int nq, int64_t ndb, int dim, int k);
+size_t vpr_row_bytes(int dim);
+int launch_vpr_pack(const float* x, int64_t n, int dim, void* packed, hipStream_t s);
+int launch_vpr_search(VprSearchArgs a, unsigned char* scratch, float* dist, int64_t* idx, hipStream_t s);
+
 // ---- small layout / elementwise kernels -----------------------------------------------------
 int launch_preprocess(const unsigned char* src, float* dst, int B, int Hs, int Ws, int H, int W, hipStream_t s);
 int launch_l2norm_channels(float* x, long npix, int C, hipStream_t s);
