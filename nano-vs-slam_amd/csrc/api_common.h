@@ -1,0 +1,33 @@
+// What every host file behind the C ABI shares: the thread-local error message, HIP_TRY and the workspace alignment.
+// No HIP header here (model_desc.cpp compiles without one); HIP_TRY expands where <hip/hip_runtime.h> is included.
+#pragma once
+#include <cstdarg>
+#include <cstddef>
+#include <cstdio>
+
+#include "../../include/kp2d.h"
+
+namespace kp2d {
+
+void set_last_error(const char* msg);   // thread-local message behind kp2d_last_error() (kp2d_api.cpp)
+
+inline int fail(int code, const char* fmt, ...) {
+  char buf[1024];
+  va_list ap;
+  va_start(ap, fmt);
+  vsnprintf(buf, sizeof buf, fmt, ap);
+  va_end(ap);
+  set_last_error(buf);
+  return code;
+}
+
+constexpr size_t ALIGN = 256;
+inline size_t align_up(size_t v, size_t a = ALIGN) { return (v + a - 1) / a * a; }
+
+}  // namespace kp2d
+
+#define HIP_TRY(expr)                                                                                \
+  do {                                                                                               \
+    hipError_t e_ = (expr);                                                                          \
+    if (e_ != hipSuccess) return kp2d::fail(KP2D_ERR_HIP, "%s: %s", #expr, hipGetErrorString(e_));   \
+  } while (0)

@@ -9,7 +9,7 @@
 //   tap pair (t, t'):  [xl_t | xl_t'] . [wh_t | wh_t']  +  [xh_t | xh_t'] . [wl_t | wl_t']  +  [xh_t | xh_t'] . [wh_t | wh_t']
 //   single tap t:      [xh_t | xl_t ] . [wh_t | wh_t ]  +  [xh_t | xl_t ] . [wl_t | wl_t ]      (all four cross terms)
 // i.e. 3 MFMAs per two taps + 2 for the ninth: 14 per 16-channel chunk instead of 13.5 (3.7 % padding).
-// The packer stores the nine taps of a chunk in slot order {0,1,3,4,2,5,6,7,8} (kp2d_api.cpp pack()): slots (0,1),
+// The packer stores the nine taps of a chunk in slot order {0,1,3,4,2,5,6,7,8} (model_desc.cpp pack()): slots (0,1),
 // (2,3), (6,7) are taps one pixel apart in x, slots (4,5) = taps (2,5) one row apart, slot 8 is the single.
 //
 // LDS images are planar and unpadded: input [hi plane | lo plane], each [18 rows][20 px][16 halves = 32 B]; weights
@@ -354,7 +354,7 @@ __global__ __launch_bounds__(256 * NH * NP, NH * NP == 1 ? 3 : 4) void conv3x3_f
 // Up to four INDEPENDENT layers as one launch (blockIdx.z = layer; a workgroup beyond its layer's grid leaves at once).  A single
 // frame's forward is a chain of ~25 dependent launches, each as long as ONE workgroup's serial chain (8-10 us whatever it
 // computes): layers of different heads that wait for the same predecessor cost one such latency together instead of one each
-// (kp2d_api.cpp groups them on small grids).  Same code per layer as its own launch: bit-identical.
+// (plan.cpp groups them on small grids).  Same code per layer as its own launch: bit-identical.
 struct ConvMultiArgs { ConvArgs a[4]; int n; };
 __global__ __launch_bounds__(256, 3) void conv3x3_f16x3_multi_kernel(const ConvMultiArgs m) {
   const ConvArgs& a = m.a[blockIdx.z];
@@ -976,7 +976,7 @@ static int launch_ws_t(const ConvArgs& a0, const ConvChoice& c, const StemArgs& 
 }
 template <bool S16OUT>
 static int launch_ws(const ConvArgs& a, const ConvChoice& c, hipStream_t s) {
-  if (a.stem_x) {      // conv1a computed by the staging waves (kp2d_api.cpp hands its arguments over instead of launching it)
+  if (a.stem_x) {      // conv1a computed by the staging waves (plan.cpp hands its arguments over instead of launching it)
     const StemArgs st{a.stem_x, a.stem_w, a.stem_scale, a.stem_shift, a.stem_wscale, a.stem_act};
     return launch_ws_t<S16OUT, true>(a, c, st, s);
   }
@@ -1027,7 +1027,7 @@ int launch_conv3x3_f16x3_multi(const ConvArgs* list, int n, hipStream_t s) {
     if (a.taps != 9 || a.prec != 1 || a.in0.fmt != 0 || a.store == ST_S16P || a.store == ST_S16P_POOL) return -1000;
     if (a.in0.rs != (long)a.W * a.in0.ps || (a.in1.c > 0 && a.in1.rs != (long)a.W * a.in1.ps)) return -1000;
     if ((long)a.H * a.W * (a.in0.ps > a.in1.ps ? a.in0.ps : a.in1.ps) * 4 >= BUF_LIMIT) return -1000;
-    if (!(a.npad == 32 || a.ng32)) return -1000;                       // 32-channel groups (kp2d_api.cpp: small grids)
+    if (!(a.npad == 32 || a.ng32)) return -1000;                       // 32-channel groups (plan.cpp: small grids)
     a.tiles_x = (a.W + 15) / 16;
     a.tiles_y = (a.H + 7) / 8;
     const int nx = a.tiles_x * a.tiles_y * a.B, ny = a.npad / 32;

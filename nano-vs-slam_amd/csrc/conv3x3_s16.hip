@@ -305,7 +305,7 @@ __global__ __launch_bounds__(D_THREADS, 3) void conv3x3_f16x3_s16_kernel(const C
       // tile (m, n): lane (lp, lg) holds channel 16 n + lp, pixels (row 4 wr + m, columns 16 ph + 4 lg .. + 3).  Plain logits
       // (no activation), every channel into out0 [B, cout, H, W]; W is a multiple of 4, so a lane's four pixels are inside or
       // outside the map together.  (Not for a layer that also writes the dense class map, ConvArgs::ids_out: its channels sit
-      // in 32 different lanes here, and the argmax by DPP rotations cost more than the form gains — kp2d_api.cpp s16_planar)
+      // in 32 different lanes here, and the argmax by DPP rotations cost more than the form gains — plan.cpp s16_planar)
       const int obs = a.cout * H * W;
       const __amdgpu_buffer_rsrc_t rs0 = __builtin_amdgcn_make_buffer_rsrc(a.out0 + (size_t)it.b * obs, 0, obs * 4, 0x00020000);
       const int x = it.x0 + 16 * ph + 4 * lg;

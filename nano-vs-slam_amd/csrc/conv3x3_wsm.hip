@@ -83,7 +83,7 @@ __global__ __launch_bounds__(M_THREADS, 3) void conv3x3_f16x3_wsm_kernel(const C
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const bool consumer = wave < 8;                    // wave-uniform by construction (see the barrier contract above)
   // Tile space.  A tile is 16 rows x 32 columns of (H, W); with a.wsm_tr those are the map's COLUMNS x ROWS — the tile walks
-  // the map transposed (tile row = map column), the weight slab has its taps transposed to match (kp2d_api.cpp w16t), and
+  // the map transposed (tile row = map column), the weight slab has its taps transposed to match (model_desc.cpp w16t), and
   // only the two places that form global addresses know: the staging waves' pixel index and the epilogue's (y, x).
   // Why: a 30 x 40 map is 2 x 2 tiles with 8 of the second tile column's 32 columns inside (24 quarter-SIMD units of matrix
   // work per frame for 18.75 of pixels); as 40 x 30 it is 3 x 1 tiles, the last with 8 of 16 rows = half of the waves, none
@@ -625,7 +625,7 @@ static int wsm_launch_one(const ConvArgs& a, int grid, long nitems, long ntiles,
 template <int NN>
 static int wsm_launch(const ConvArgs& a, int grid, long nitems, long ntiles, hipStream_t s) {
   if constexpr (NN == 4) {
-    if (a.in0.fmt == 1) {             // S16P inputs (the plan's big-grid layout, kp2d_api.cpp)
+    if (a.in0.fmt == 1) {             // S16P inputs (the plan's big-grid layout, plan.cpp)
       switch (a.store) {
         case ST_NHWC: return wsm_launch_one<ST_NHWC, 4, true>(a, grid, nitems, ntiles, s);
         case ST_NHWC_POOL: return wsm_launch_one<ST_NHWC_POOL, 4, true>(a, grid, nitems, ntiles, s);

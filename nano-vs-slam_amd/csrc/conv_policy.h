@@ -1,5 +1,5 @@
 // Host-side policy of the split-fp16 3x3 convolutions (prec = 1, taps = 9): which tile form runs a layer, on how many
-// workgroups, and what the plan (kp2d_api.cpp build()) may assume before it picks the activation layouts.  Every decision is
+// workgroups, and what the plan (plan.cpp build()) may assume before it picks the activation layouts.  Every decision is
 // made here once; the launchers in conv3x3_f16.hip, conv3x3_wsm.hip and conv3x3_s16.hip only launch what it chose.
 // Plain C++: it takes the CU count and the stream-lane count as arguments and never asks the device
 // (tests/test_conv_policy.py compiles it with g++).

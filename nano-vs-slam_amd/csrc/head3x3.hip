@@ -22,7 +22,7 @@ constexpr int HD_G = HD_HY * HD_HX * (HD_SC / 4);     // float4 granules of a st
 constexpr int HD_IT = (HD_G + 255) / 256;
 }  // namespace
 
-// a.w: [chunk][tap][4][16] floats (kp2d_api.cpp pack(): ConvPack::wd_off), a.scale / a.shift: [cout]
+// a.w: [chunk][tap][4][16] floats (model_desc.cpp pack(): ConvPack::wd_off), a.scale / a.shift: [cout]
 // LDS (dynamic): s_in [HD_HY * HD_ROW] floats (30,720 B), then s_part [4 * CO * 64]
 template <int CO>
 __device__ __forceinline__ void head3x3_body(const ConvArgs& a, float* const s_in) {

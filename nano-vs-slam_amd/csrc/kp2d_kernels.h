@@ -1,4 +1,4 @@
-// Internal launch interface between the C-ABI host code (kp2d_api.cpp) and the HIP kernels.
+// Internal launch interface between the host code (plan.cpp, kp2d_api.cpp, lightglue_api.cpp) and the HIP kernels.
 // Not part of the public ABI (that is include/kp2d.h).
 #pragma once
 #include <hip/hip_runtime.h>
@@ -122,8 +122,6 @@ struct AttnArgs {
                        // of both directions in one launch: items [0,B/2) are image 0, [B/2,B) image 1)
 };
 int launch_attention(const AttnArgs& a, hipStream_t s);
-
-void set_last_error(const char* msg);   // thread-local message behind kp2d_last_error() (kp2d_api.cpp)
 
 // ---- LightGlue matcher (lightglue/lightglue.py; kernels in lightglue.hip) -----------------------
 struct LgPosArgs {

@@ -9,7 +9,7 @@ convs.4 / .6, the two-source layers (confAa, convs.5, convs.7 read ``cat(upsampl
 ``maxpool2`` of conv3b's full-resolution tap, the parts of the merged ``heads.first`` (tapped under the heads' own
 names), and the planar API outputs ``score``, ``coord``, ``feat``, ``seg`` behind the heads' last layers.
 
-The epilogue scale / shift are the fp32 values the weight upload folds BatchNorm into (kp2d_api.cpp bn_fold:
+The epilogue scale / shift are the fp32 values the weight upload folds BatchNorm into (model_desc.cpp bn_fold:
 ``s = gamma / sqrt(var + 1e-5f)``, ``sh = beta - mean * s``, both fp32): they are part of the weights the kernel is
 given, not of its arithmetic, and are applied here in float64.
 
@@ -154,7 +154,7 @@ def layer_graph(cfg):
 
 
 def merged_parts(cfg):
-    """The layers the merged first launch of the heads ("heads.first", kp2d_api.cpp describe()) computes."""
+    """The layers the merged first launch of the heads ("heads.first", model_desc.cpp describe()) computes."""
     parts = ["score_loc_head.convDa"] if cfg["v3"] else ["score_head.convDa", "loc_head.convDa", "desc_head.convA"]
     return parts + ["seg_head.convs.0", "vlad_head.convlad1"]
 
@@ -187,7 +187,7 @@ def tap_shapes(cfg, sd, H, W):
 # reference and bound
 # ---------------------------------------------------------------------------------------------------------------------
 def fold(sd, sp):
-    """The fp32 epilogue scale and shift the weight upload gives the kernel (kp2d_api.cpp bn_fold / the bias layers)."""
+    """The fp32 epilogue scale and shift the weight upload gives the kernel (model_desc.cpp bn_fold / the bias layers)."""
     co = sd[sp.weight_key()].shape[0]
     if not sp.bn:
         b = sd.get(f"{sp.name}.bias")

@@ -10,11 +10,11 @@ import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
-# The plan of KP2DTiny-S (backbone conv1b .. conv4b and the heads' merged first layer) as kp2d_api.cpp build() / conv_args()
+# The plan of KP2DTiny-S (backbone conv1b .. conv4b and the heads' merged first layer) as plan.cpp build() / Plan::conv_args()
 # lay it out for one sub-batch of B frames on `lanes` stream lanes, each layer's choice printed as "layer variant grid".
 # The plan side is a copy, not build() itself: main() mirrors build()'s `stem`, `s16`, `small_heads` / `big_wsm` / `merged` and
-# `s16_all` conditions (default options, KP2DTiny-S, float frames) and layer() mirrors conv_args()'s `wsm_force` and ng32
-# rules.  A change to those in kp2d_api.cpp must be made here too.
+# `s16_all` conditions (default options, KP2DTiny-S, float frames) and layer() mirrors Plan::conv_args()'s `wsm_force` and ng32
+# rules.  A change to those in plan.cpp must be made here too.
 SRC = r"""
 #include <cstdio>
 #include <cstdlib>

@@ -1175,7 +1175,7 @@ def test_split_activation_backbone_stage_equals_the_fp32_activation_path(config,
 @pytest.mark.parametrize("B", [1, 2])
 def test_single_frame_netvlad_on_the_side_stream_equals_in_line(B):
     """Small grids run the heads level by level; NetVLAD's three launches go to a model-owned side stream beside the
-    segmentation head's chain (kp2d_api.cpp build(): fork after level 2, join before the forward returns; in line under
+    segmentation head's chain (plan.cpp build(): fork after level 2, join before the forward returns; in line under
     stream capture).  Same kernels on the same data: every output bit-identical to side_overlap = 0 — also back to back,
     where a missing join or a scratch buffer released before the side stream is done would show as a changed descriptor."""
     model, _ = product_model("S", False, 28)
@@ -1214,7 +1214,7 @@ _S16ALL_TAPS = [("backbone.conv3b", 64, 2), ("backbone.conv4a", 64, 4), ("backbo
     (5, 96, 256, True),
 ])
 def test_all_split_activations_equal_the_fp32_activation_layout(B, H, W, forced):
-    """Big grids keep EVERY tensor a warp-specialised split-fp16 3x3 layer reads as S16P (kp2d_api.cpp build(): conv3b's two
+    """Big grids keep EVERY tensor a warp-specialised split-fp16 3x3 layer reads as S16P (plan.cpp build(): conv3b's two
     outputs, conv4a / 4b, the desc / seg / vlad slices of the merged first layer, both pixel-shuffled tensors, convs.5,
     convlad2, confAa's and convs.7's outputs), copied into LDS by LDS-DMA (conv3x3_wsm.hip IN16, conv3x3_s16.hip) — against the same forward with s16_all = 0: every
     consumer multiplies the halves its own staging would have produced, so every OUTPUT is bit-identical; the profile says
