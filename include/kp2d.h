@@ -249,40 +249,19 @@ int kp2d_set_tap(kp2d_model* m, const char* layer, float* dst, size_t capacity_f
 int kp2d_set_seg_ids(kp2d_model* m, int64_t* ids, size_t capacity);
 /* frames per internal sub-batch (0 = automatic).  Intermediates of one sub-batch stay in the 256 MB Infinity Cache. */
 int kp2d_set_chunk_frames(kp2d_model* m, int frames);
-/* Tuning knobs of the engine (never needed for correct results; used by the A/B scripts and the parity tests to force a
- * kernel form).  Keys:
- *   "wsm_min_items"  least number of (16 x 32 pixel tile, 64-channel group) work items of a launch for the
- *                    warp-specialised persistent form of the multi-chunk 3x3 layers (conv3x3_wsm.hip);
- *                    0 = automatic (more than two rounds of the launch's workgroups), -1 = never.
- *   "ws_min_tiles"   least 16 x 32 pixel tiles of a launch for the warp-specialised form of backbone.conv1b
- *                    (conv3x3_f16x3_ws_kernel); 0 = default (1024).
- *   "wsm_grid"       most workgroups per launch of the persistent forms (conv3x3_wsm.hip, conv3x3_s16.hip and conv1b's;
- *                    0 = automatic: CUs / stream lanes, conv1b's form the whole chip).
- *   "lanes"          stream lanes one forward splits its batch over (sub-batches run side by side on internal streams;
- *                    a workspace sized before the change stays valid only for lane counts <= the one it was sized
- *                    for): 0 = default (KP2D_LANES if set, else 2).  A caller that keeps two batches in flight on two
- *                    streams of its own (pipeline.BatchStream: each with its own workspace) sets 1 — the two
- *                    forwards then fill each other's launch tails, which two lanes of ONE forward (same layer at the
- *                    same time) cannot: 22.9k -> 23.4k frames/s at 64 x 240 x 320.
- *   "wsm_transposed" that form's tiles walk the map transposed (tile rows = map columns, the taps of the weight pack
- *                    transposed to match): 0 = never (default), 1 = always, 2 = where the matrix-time model says it is
- *                    cheaper (30 x 40 maps: 3 x 1 tiles instead of 2 x 2).  It sums the nine taps in another order, so
- *                    results differ from every other tile form in the last bits — which is why it is opt-in: with it
- *                    off, outputs are bit-identical whatever the batch size, lane count or tile form
- *                    ("conv3x3_f16x3<wsm>t" in the profile).
- *   "s16_all"        1 (default): big grids keep every tensor the warp-specialised 3x3 layers read as the fp16 halves of the
- *                    split (LDS-DMA staging, conv3x3_wsm.hip; bit-identical); 0: only inside the backbone's 32-channel stage.
- *   "side_overlap"   1 (default): a plain single-frame forward runs NetVLAD on a model-owned side stream beside the
- *                    segmentation head (never under stream capture; the stream is created on first use); 0: in line — and
- *                    the stream is destroyed (a process that keeps several streams busy wants the hardware queue back).
- *   "stem_fusion", "s16_min_items", "multi_launch", "mff_fused": README.md's table of knobs.
- * Setting a tile-form option back to 0 restores the built-in automatic policy (nano-vs-slam_amd/csrc/conv_policy.h).
- * KP2D_WSM (0: -1, n: n), KP2D_WSM_GRID, KP2D_WSM_TR, KP2D_S16=0 (s16_min_items -1), KP2D_S16ALL=0 and KP2D_MULTI=0 set
- * the initial values of "wsm_min_items", "wsm_grid", "wsm_transposed", "s16_min_items", "s16_all" and "multi_launch"
- * when kp2d_create runs.
- * Unknown keys return KP2D_ERR_ARG.  kp2d_profile_get reports the tile form each conv launch took behind its kernel
- * family ("conv3x3_f16x3<wsm>", "conv3x3_f16x3<2,1,16>", ...). */
+/* Tuning options of the engine (never needed for correct results; the A/B scripts and the parity tests use them to force a
+ * kernel form).  Keys: "wsm_min_items", "ws_min_tiles", "wsm_grid", "wsm_transposed", "s16_min_items", "s16_all",
+ * "multi_launch", "mff_fused", "stem_fusion", "side_overlap", "lanes"; kp2d_option_name lists them (KP2D_ERR_ARG past the last
+ * index).  Meaning, default and range of each, and the KP2D_* environment variable that gives it its initial value when
+ * kp2d_create runs, are the rows of ONE table: kOptions in nano-vs-slam_amd/csrc/options.h (README.md's table of knobs
+ * describes the variables).  Setting a tile-form option back to 0 restores the built-in automatic policy
+ * (nano-vs-slam_amd/csrc/conv_policy.h); "lanes" = 0 restores the handle's initial lane count.  An unknown key or a value
+ * outside the row's range returns KP2D_ERR_ARG and changes nothing.  kp2d_get_option reads the value in effect ("lanes": the
+ * lane count, never 0).  kp2d_profile_get reports the tile form each conv launch took behind its kernel family
+ * ("conv3x3_f16x3<wsm>", "conv3x3_f16x3<2,1,16>", ...). */
 int kp2d_set_option(kp2d_model* m, const char* key, long value);
+int kp2d_get_option(const kp2d_model* m, const char* key, long* value);
+int kp2d_option_name(int index, const char** key);
 
 /* ---- Place recognition: flat squared-L2 top-k over global descriptors (nano-vs-slam_amd/csrc/vpr.hip) ----------
  * Replaces the faiss.IndexFlatL2 search of the reference's evaluate_global_descriptor

@@ -8,9 +8,8 @@
 //                              written; K/V are walked in 64-key LDS chunks with an online softmax.
 //  * dwconv3x3_kernel          depthwise 3x3 + bias of MixFeedForward's DsConv2d (segformer.py:45-59)
 // The 1x1 convolutions (to_q, to_out, MixFFN) and the 2x2 stride-2 to_kv run through conv3x3.hip with taps = 1.
-#include <cstdlib>
-
 #include "kp2d_kernels.h"
+#include "options.h"
 
 namespace kp2d {
 
@@ -664,16 +663,15 @@ int launch_attention(const AttnArgs& a, hipStream_t s) {
   if (a.C % a.heads || d > 64 || (d & 3) || (a.C & 3)) return -1402;
   if (a.prec == 1 && d <= 16) {
     // short sequences that leave most of the chip idle in the query-tiled kernel: split the keys over the waves
-    static const long ks_max = getenv("KP2D_ATT_KSPLIT") ? atol(getenv("KP2D_ATT_KSPLIT")) : 256;
-    if ((long)((a.S + 127) / 128) * a.heads * a.B < ks_max && a.T >= 128) {
+    if ((long)((a.S + 127) / 128) * a.heads * a.B < tuning().att_ksplit && a.T >= 128) {
       hipLaunchKernelGGL(attention_ksplit_kernel, dim3((a.S + 31) / 32, a.heads, a.B), dim3(256), 0, s, a);
       return (int)hipGetLastError();
     }
     // 256 queries per workgroup halve the K / V staging per query (18 % of the kernel at 128); short sequences
     // keep 128 so that the grid still covers the chip
-    static const int big = getenv("KP2D_ATT_Q") ? atoi(getenv("KP2D_ATT_Q")) : 256;
+    const int big = tuning().att_q;
     // (tiles * pairs, 1, 1): XCD-affine pair order (see the kernel); needs pairs % 8 == 0
-    const bool affine = (a.heads * a.B) % 8 == 0 && !(getenv("KP2D_ATT_AFFINE") && getenv("KP2D_ATT_AFFINE")[0] == '0');
+    const bool affine = (a.heads * a.B) % 8 == 0 && tuning().att_affine;
     if (big == 256 && (long)((a.S + 255) / 256) * a.heads * a.B >= 512) {
       const int tiles = (a.S + 255) / 256;
       hipLaunchKernelGGL((attention_split_kernel<512, 6>), affine ? dim3(tiles * a.heads * a.B) : dim3(tiles, a.heads, a.B), dim3(512), 0, s, a);

@@ -55,23 +55,7 @@ int kp2d_create(const kp2d_config* cfg, kp2d_model** out) {
   if (cfg->n_classes < 1 || cfg->n_classes > 32) { delete m; return fail(KP2D_ERR_UNSUPPORTED, "n_classes must be in [1,32]"); }
   int rc = describe(m);
   if (rc != KP2D_OK) { delete m; return rc; }
-  const char* nlanes = getenv("KP2D_LANES");
-  if (nlanes) m->lanes = std::max(1, std::min(8, atoi(nlanes)));
-  m->lanes_default = m->lanes;
-  if (getenv("KP2D_SIDE") && getenv("KP2D_SIDE")[0] == '0') m->side_overlap = false;      // (A/B knob)
-  if (getenv("KP2D_MFF") && getenv("KP2D_MFF")[0] == '0') m->mff_fused = false;
-  if (getenv("KP2D_STEM")) m->stem_fusion = std::max(0, std::min(2, atoi(getenv("KP2D_STEM"))));
-  if (getenv("KP2D_DBG")) m->dbg = atoi(getenv("KP2D_DBG"));
-  if (getenv("KP2D_LANE_PRIORITY")) m->lane_prio = atoi(getenv("KP2D_LANE_PRIORITY"));
-  // A/B switches of the conv path: initial values of their kp2d_set_option equivalents (conv_policy.h reads only options)
-  long v = 0;
-  auto env = [&v](const char* name) { const char* e = getenv(name); if (e && *e) v = atol(e); return e && *e; };
-  if (env("KP2D_WSM") && v >= 0) m->wsm_min = v == 0 ? -1 : (int)std::min(v, 0x7fffffffL);
-  if (env("KP2D_WSM_GRID") && v > 0) m->wsm_grid = (int)std::min(v, 65536L);
-  if (env("KP2D_WSM_TR") && v >= 0 && v <= 2) m->wsm_tr = (int)v;
-  if (env("KP2D_S16") && v == 0) m->s16_min = -1;
-  if (env("KP2D_S16ALL") && v == 0) m->s16_all = false;
-  if (env("KP2D_MULTI") && v == 0) m->multi_launch = false;
+  options_from_env(*m, [](const char* name) -> const char* { return getenv(name); });
   *out = m;
   return KP2D_OK;
 }
@@ -491,73 +475,27 @@ int kp2d_set_tap(kp2d_model* m, const char* layer, float* dst, size_t capacity_f
 
 int kp2d_set_option(kp2d_model* m, const char* key, long value) {
   if (!m || !key) return fail(KP2D_ERR_ARG, "bad argument");
-  const std::string k = key;
   m->plan_cache.clear();      // (an option may change the plan: sizes are memoised per setting)
-  if (k == "wsm_min_items") {
-    if (value > 0x7fffffffL || value < -1) return fail(KP2D_ERR_ARG, "wsm_min_items out of range");
-    m->wsm_min = (int)value;
-    return KP2D_OK;
+  const int rc = set_option(*m, key, value);
+  if (rc == KP2D_OK && !m->side_overlap && m->side_stream) {      // give the stream (and the hardware queue it maps to) back
+    DeviceGuard guard(m->cfg.device);
+    (void)hipStreamSynchronize(m->side_stream);
+    (void)hipStreamDestroy(m->side_stream);
+    (void)hipEventDestroy(m->side_fork);
+    (void)hipEventDestroy(m->side_join);
+    m->side_stream = nullptr; m->side_fork = m->side_join = nullptr;
   }
-  if (k == "s16_min_items") {     // conv3x3_s16.hip (split activations through the backbone's 32-channel stage): 0 automatic, N from N tiles, -1 never
-    if (value > 0x7fffffffL || value < -1) return fail(KP2D_ERR_ARG, "s16_min_items out of range");
-    m->s16_min = (int)value;
-    return KP2D_OK;
-  }
-  if (k == "mff_fused") {         // 1 (default): depthwise 3x3 -> 1x1 -> GELU -> 1x1 of the attention modules' MixFeedForward as one launch
-    if (value < 0 || value > 1) return fail(KP2D_ERR_ARG, "mff_fused is 0 or 1");
-    m->mff_fused = value != 0;
-    return KP2D_OK;
-  }
-  if (k == "stem_fusion") {       // 1 (default): conv1a in split-fp16 products, inside conv1b's launch on big grids; 2: never fused; 0: exact-fp32 FMA kernels
-    if (value < 0 || value > 2) return fail(KP2D_ERR_ARG, "stem_fusion is 0, 1 or 2");
-    m->stem_fusion = (int)value;
-    return KP2D_OK;
-  }
-  if (k == "side_overlap") {      // 1 (default): single frames run NetVLAD on a side stream beside the segmentation head; 0: in line
-    if (value < 0 || value > 1) return fail(KP2D_ERR_ARG, "side_overlap is 0 or 1");
-    m->side_overlap = value != 0;
-    if (!m->side_overlap && m->side_stream) {      // give the stream (and the hardware queue it maps to) back
-      DeviceGuard guard(m->cfg.device);
-      (void)hipStreamSynchronize(m->side_stream);
-      (void)hipStreamDestroy(m->side_stream);
-      (void)hipEventDestroy(m->side_fork);
-      (void)hipEventDestroy(m->side_join);
-      m->side_stream = nullptr; m->side_fork = m->side_join = nullptr;
-    }
-    return KP2D_OK;
-  }
-  if (k == "s16_all") {      // 1 (default): S16P tensors between the warp-specialised 3x3 layers of big grids; 0: only inside the 32-channel stage
-    if (value < 0 || value > 1) return fail(KP2D_ERR_ARG, "s16_all is 0 or 1");
-    m->s16_all = value != 0;
-    m->plan_cache.clear();
-    return KP2D_OK;
-  }
-  if (k == "multi_launch") {      // 1 (default): layers of different heads that wait for the same predecessor run as one launch on small grids
-    if (value < 0 || value > 1) return fail(KP2D_ERR_ARG, "multi_launch is 0 or 1");
-    m->multi_launch = value != 0;
-    return KP2D_OK;
-  }
-  if (k == "ws_min_tiles") {
-    if (value < 0 || value > 0x7fffffffL) return fail(KP2D_ERR_ARG, "ws_min_tiles out of range");
-    m->ws_min = (int)value;
-    return KP2D_OK;
-  }
-  if (k == "lanes") {      // stream lanes of one forward: 0 = the default (KP2D_LANES, else 2); 1 when the CALLER keeps several batches in flight
-    if (value < 0 || value > 8) return fail(KP2D_ERR_ARG, "lanes is 0 (default) .. 8");
-    m->lanes = value == 0 ? m->lanes_default : (int)value;
-    return KP2D_OK;
-  }
-  if (k == "wsm_transposed") {      // conv3x3_wsm.hip: tiles walk the map transposed — 0 never (default), 1 always, 2 where cheaper
-    if (value < 0 || value > 2) return fail(KP2D_ERR_ARG, "wsm_transposed is 0, 1 or 2");
-    m->wsm_tr = (int)value;
-    return KP2D_OK;
-  }
-  if (k == "wsm_grid") {
-    if (value < 0 || value > 65536) return fail(KP2D_ERR_ARG, "wsm_grid out of range");
-    m->wsm_grid = (int)value;
-    return KP2D_OK;
-  }
-  return fail(KP2D_ERR_ARG, "unknown option '%s'", key);
+  return rc;
+}
+
+int kp2d_get_option(const kp2d_model* m, const char* key, long* value) {
+  if (!m || !key || !value) return fail(KP2D_ERR_ARG, "null argument");
+  return get_option(*m, key, value);
+}
+
+int kp2d_option_name(int index, const char** key) {
+  if (!key || !(*key = option_name(index))) return fail(KP2D_ERR_ARG, "option index out of range");
+  return KP2D_OK;
 }
 
 int kp2d_set_seg_ids(kp2d_model* m, int64_t* ids, size_t capacity) {

@@ -15,9 +15,9 @@
 //  lg_sim_kernel        sim = f0 f1^T (:391) + per-tile row / column log-sum-exp partials
 //  lg_finalize_kernel   sigmoid_log_double_softmax (:363-376) + per-tile row / column max, argmax (filter_matches :403-404)
 //  lg_filter_kernel     mutual check, threshold, match scores (:405-416)
-#include <cstdlib>
 #include "kp2d_kernels.h"
 #include "device_guard.h"
+#include "options.h"
 
 namespace kp2d {
 
@@ -416,8 +416,7 @@ int launch_lg_tail(const LgTailArgs& a, hipStream_t s) {
   if (!a.ctx && !a.nn) return -1807;
   // four waves per workgroup also at one image pair (2048 rows = 32 workgroups): one-wave workgroups spread wider but
   // each stages the 42 KB of operands with 64 lanes — 0.236 vs 0.204 ms per forward
-  static const int forced = getenv("KP2D_LG_TAIL_NW") ? atoi(getenv("KP2D_LG_TAIL_NW")) : 0;
-  const int nw = forced ? forced : 4;
+  const int nw = tuning().lg_tail_nw ? tuning().lg_tail_nw : 4;
   const size_t lds = (size_t)(LG_IMG_O + LG_IMG_1 + LG_IMG_2 + LG_IMG_N) * 2 + LG_TAIL_VEC * sizeof(float);
   const dim3 grid((a.rows + 16 * nw - 1) / (16 * nw));
   if (nw == 4) hipLaunchKernelGGL(lg_tail_mfma_kernel<4>, grid, dim3(256), lds, s, a);

@@ -6,7 +6,6 @@
 
 #include <cmath>
 #include <cstdio>
-#include <cstdlib>
 #include <map>
 #include <string>
 #include <vector>
@@ -14,6 +13,7 @@
 #include "api_common.h"
 #include "device_guard.h"
 #include "kp2d_kernels.h"
+#include "options.h"
 
 using namespace kp2d;
 
@@ -347,11 +347,11 @@ int kp2d_lg_forward_counts(kp2d_lg* m, const float* kpts0, const float* kpts1, c
     return KP2D_OK;
   };
   // D = 32 (configs S, A): out_proj / to_out + ffn + residual as ONE row-local kernel (lightglue.hip lg_tail_kernel)
-  static const bool fuse_tail = !(getenv("KP2D_LG_FUSE") && getenv("KP2D_LG_FUSE")[0] == '0');
+  const bool fuse_tail = tuning().lg_fuse;
   // `next`: the token-wise projection that follows the block (the cross block's [to_qk | to_v], the next layer's Wqkv
   // with rotary, the final projection) runs in the tail's launch on the rows it has just updated: 8 launches fewer
   // per forward than one lg_linear per projection (the matcher is a chain of ~35 dependent launches of ~10 us)
-  static const bool fuse_next = !(getenv("KP2D_LG_FUSE_NEXT") && getenv("KP2D_LG_FUSE_NEXT")[0] == '0');
+  const bool fuse_next = tuning().lg_fuse_next;
   auto tail = [&](const Lin& proj, const Ffn& f, const char* what, const Lin* next, float* nout, int nos, int nvalid,
                   bool rotary) -> int {
     LgTailArgs t{};

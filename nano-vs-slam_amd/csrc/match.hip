@@ -15,9 +15,8 @@
 //   pairs_kernel    compacts the matched rows of a pair into (x0, y0, x1, y1) / (q, t) / distance lists (train order)
 // Batched over B frame pairs with per-pair descriptor counts, so the per-frame D2H copy + CPU matcher of the
 // reference disappears.  HBM-light (descriptors are tiny); bound by VALU: n0*n1*C*3 ops per pair.
-#include <cstdlib>
-
 #include "kp2d_kernels.h"
+#include "options.h"
 
 namespace kp2d {
 
@@ -435,8 +434,7 @@ static int knn2(const MatchArgs& a, bool reverse, int32_t* idx, float* dist, flo
   const int max0 = reverse ? a.max1 : a.max0, max1 = reverse ? a.max0 : a.max1;
   // matrix-core form from 256 train rows (below that a query meets one or two LDS tiles and the exact pass dominates);
   // KP2D_MATCH_MFMA=0: always the VALU form (A/B)
-  static const bool mfma_on = !(getenv("KP2D_MATCH_MFMA") && getenv("KP2D_MATCH_MFMA")[0] == '0');
-  const bool mfma = mfma_on && max1 >= 256;
+  const bool mfma = tuning().match_mfma && max1 >= 256;
   const int qpw = mfma ? MM_Q : MQ, rows = mfma ? mm_rows(a.C) : mt_rows(a.C);
   const long wgs = (long)((max0 + qpw - 1) / qpw) * a.B;
   int nz = 1;

@@ -11,10 +11,9 @@
 //   pass 2: grid (B); sums the partials in split order, subtracts rowsum * centroid, does both
 //           normalisations with wavefront shuffles + one LDS exchange.
 // The input is the NHWC output of vlad_head.convlad3, so a pixel's C channels are one contiguous line.
-#include <cstdlib>
-
 #include "kp2d_kernels.h"
 #include "device_guard.h"
+#include "options.h"
 
 namespace kp2d {
 
@@ -23,7 +22,7 @@ constexpr int VT = 64;  // pixels per LDS tile
 int netvlad_nsplit(int S) {
   // Depends on the frame size only: the order of the partial sums (and with it the last bits of the descriptor)
   // must not change with the batch or sub-batch a frame happens to travel in (test_full_size_properties).
-  static const int per = getenv("KP2D_VLAD_PX") ? atoi(getenv("KP2D_VLAD_PX")) : 320;   // pixels per workgroup (tuning knob)
+  const int per = tuning().vlad_px;   // pixels per workgroup (tuning knob)
   int n = (S + per - 1) / per;
   return n < 1 ? 1 : n;
 }
@@ -519,8 +518,7 @@ int launch_netvlad(const VladArgs& a, hipStream_t s) {
   if (a.K > 64 || (a.K & 3) || (a.C & 3) || a.K * a.C > 8192 || a.K < 4) return -1100;
   if ((a.K == 32 || a.K == 64) && a.C <= 64) {
     const int kt = a.K / 32;
-    static const bool split_on = !(getenv("KP2D_VLAD_SPLIT") && getenv("KP2D_VLAD_SPLIT")[0] == '0');
-    const bool split = a.prec == 1 && split_on;
+    const bool split = a.prec == 1 && tuning().vlad_split;
     const dim3 grid(a.nsplit * (a.tps > 1 ? a.tps : 1), a.B);
     if (split) {
       const size_t lds = (size_t)(VT * VP + VT * AP + VT * HP) * sizeof(float);      // (hi | lo half images = HP floats per row)

@@ -12,6 +12,7 @@
 #include "api_common.h"
 #include "kp2d_kernels.h"
 #include "model_desc.h"
+#include "options.h"
 
 namespace kp2d {
 namespace plan {
@@ -25,37 +26,18 @@ struct ProfRec {
 }  // namespace plan
 }  // namespace kp2d
 
-struct kp2d_model : kp2d::ModelDesc {
+struct kp2d_model : kp2d::ModelDesc, kp2d::Options {   // (options.h: the tuning options, their defaults and variables)
   float* blob = nullptr;
   bool finalized = false;
   int chunk_frames = 0;
-  // The options start at these defaults; kp2d_create overrides them from the environment (read there, once per handle) and
-  // kp2d_set_option changes them afterwards.
-  int ws_min = 0;         // "ws_min_tiles": least tiles of a launch for the warp-specialised conv1b form (0 = 1024)
-  int wsm_grid = 0;       // "wsm_grid": most workgroups per launch of the persistent forms (0 = one per CU and lane)
-  int wsm_tr = 0;         // "wsm_transposed"
-  int wsm_min = 0;        // "wsm_min_items": 0 = automatic (conv_policy.h), < 0 = never (conv3x3_wsm.hip)
-  bool mff_fused = true;  // "mff_fused" / KP2D_MFF: MixFeedForward's tail as one launch (mff_tail.hip)
-  // "stem_fusion" / KP2D_STEM: the first layer — 1 (default): split-fp16 products, computed inside conv1b's launch on
-  // big grids (conv3x3_f16.hip STEM) and by conv1a_mfma_kernel otherwise (the same bits); 2: the same arithmetic, never fused; 0: round 4's
-  // exact-fp32 FMA kernels (conv1a_kernel / conv1a_u8_kernel)
-  int stem_fusion = 1;
-  bool multi_launch = true;   // "multi_launch": independent layers of a level as one launch on small grids
-  bool s16_all = true;        // "s16_all": big grids keep every tensor the warp-specialised 3x3 layers read as S16P (build())
-  int s16_min = 0;        // "s16_min_items": conv3x3_s16.hip — 0 = automatic (three rounds of tiles per workgroup), N = from N tiles, < 0 = never
-  int dbg = 0;            // KP2D_DBG: ConvArgs::dbg (the timing-ablation build's phase switches)
-  int lane_prio = 0;      // KP2D_LANE_PRIORITY=-1: lane streams from the high-priority pool of hardware queues — an A/B knob, profiles/r5_hw_queues.txt
   int precision = KP2D_PREC_F16X3;
   std::map<uint64_t, size_t> plan_cache;
-  int lanes = 2;          // independent sub-batches run concurrently on this many HIP streams (KP2D_LANES); +3 %
-  int lanes_default = 2;  // what kp2d_set_option("lanes", 0) restores
-  std::vector<hipStream_t> lane_streams;
+  std::vector<hipStream_t> lane_streams;   // Options::lanes: independent sub-batches run concurrently on that many HIP streams; +3 %
   std::vector<hipEvent_t> lane_events;
   hipEvent_t fork_event = nullptr;
   // single frames (the level schedule of build()): NetVLAD's launches on a side stream beside the segmentation head's chain
   hipStream_t side_stream = nullptr;
   hipEvent_t side_fork = nullptr, side_join = nullptr;
-  bool side_overlap = true;   // "side_overlap"
   bool profiling = false;
   int64_t* seg_ids_dst = nullptr;   // kp2d_set_seg_ids: class ids [B,1,H2,W2] written by the forward's last segmentation layer
   size_t seg_ids_cap = 0;

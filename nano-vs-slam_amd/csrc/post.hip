@@ -10,10 +10,9 @@
 //                      gluefactory/models/extractors/kp2dtiny.py:40; K1/K2 use the same SET.
 // Every float op that feeds an index decision is written with explicit round-to-nearest
 // intrinsics so hipcc's default fp-contraction cannot fuse it differently from the reference.
-#include <cstdlib>
-
 #include "conv_common.h"
 #include "device_guard.h"
+#include "options.h"
 
 namespace kp2d {
 
@@ -217,7 +216,7 @@ int launch_seg_argmax(const ArgmaxArgs& a, hipStream_t s) {
 //   a cap above 16384 on a big frame): survivors are compacted into the caller's idx row and sorted IN PLACE in
 //   global memory, keys rebuilt from score[idx] — no scratch buffer in the ABI, any k up to n.
 // ---------------------------------------------------------------------------------------------
-constexpr int TOPK_SMALL_MAX = 256;      // 256-thread workgroups up to here; beyond, 1024 threads hold one key each in the sort
+// (TOPK_SMALL_MAX, options.h: 256-thread workgroups up to there; beyond, 1024 threads hold one key each in the sort)
 constexpr int TOPK_LDS_MAX = 16384;      // keys that fit the LDS path
 
 __device__ __forceinline__ unsigned long long topk_key(float s, int idx, float thr) {
@@ -472,8 +471,7 @@ int launch_topk(const TopkArgs& a, hipStream_t s) {
   int kpow = 2;                                 // >= 2: the sort network always touches two key slots
   while (kpow < keff) kpow <<= 1;
   const size_t lds = (size_t)kpow * 8 + 16 + 260 * 4 + 1024 * 8;
-  static const int small_max = getenv("KP2D_TOPK_SMALL") ? atoi(getenv("KP2D_TOPK_SMALL")) : TOPK_SMALL_MAX;
-  if (keff <= small_max) {
+  if (keff <= tuning().topk_small) {
     hipLaunchKernelGGL(topk_kernel<256>, dim3(a.B), dim3(256), lds, s, a, kpow);
   } else {
     static PerDeviceOnce lds_once;      // per device: a handle may live on any visible device
@@ -555,10 +553,9 @@ __global__ __launch_bounds__(512) void gather_lds_kernel(const GatherArgs a) {
 
 int launch_gather(const GatherArgs& a, hipStream_t s) {
   if (a.C < 2) return -1310;      // (x, y ride on channels 0 and 1)
-  static const bool lds_on = !(getenv("KP2D_GATHER_LDS") && getenv("KP2D_GATHER_LDS")[0] == '0');
   // LDS form: selections of at least an eighth of the cells, planes that fit 64 KB in groups of 8 / 4 / 2 channels, and
   // enough frames to fill the chip with (frame, channel group) workgroups (one frame: 0.268 vs 0.265 ms with the direct form)
-  if (lds_on && (long)a.k * 8 >= a.n && (a.C & 7) == 0 && (long)a.B * (a.C / 8) >= 128) {
+  if (tuning().gather_lds && (long)a.k * 8 >= a.n && (a.C & 7) == 0 && (long)a.B * (a.C / 8) >= 128) {
     const dim3 block(512);
     if ((long)a.n * 8 * 4 <= 65536) {
       hipLaunchKernelGGL(gather_lds_kernel<8>, dim3(a.C / 8, a.B), block, (size_t)a.n * 8 * 4, s, a);
