@@ -304,6 +304,52 @@ int kp2d_vpr_search(const void* packed_db, const float* db, int64_t ndb, int dim
                     const int64_t* limit, int k, uint32_t flags, float* dist, int64_t* idx, void* scratch,
                     size_t scratch_bytes, void* stream);
 
+/* ---- k-means over descriptors (nano-vs-slam_amd/csrc/kmeans.hip) ------------------------------------------------
+ * Replaces the faiss.Kmeans fit of the reference's NetVLAD initialisation (utils/netvlad_utils.py:83-88,
+ * train_visloc.py:119-183).  Stateless like kp2d_vpr_*: caller-owned device buffers, the caller's stream, no
+ * synchronisation and no host round trip inside a call.
+ *   Algorithm: Lloyd iterations with faiss's conventions.  One kp2d_kmeans_step on x [n,dim] fp32 and
+ *     centroids_in [k,dim] fp32:
+ *     assign [n] int64, dist [n] float: every point's nearest centroid and its squared L2 distance, by kp2d_vpr_search
+ *       with the centroids as the database and k = 1, in the caller's precision (flags & KP2D_VPR_FP32 as there), in
+ *       query chunks of a fixed size.  Tie rule: equal distances go to the LOWER centroid index.  A point with a
+ *       non-finite element gets assign = -1 and belongs to no cluster.
+ *     counts [k] int64: points per cluster.  obj [1] float: the sum of dist (faiss's obj[i]: distances to the centroids
+ *       the iteration started with).
+ *     centroids_out [k,dim] (not centroids_in): a non-empty cluster's mean, sum * (1 / count) in fp32.  An empty cluster
+ *       takes faiss's split_clusters rule, in ascending cluster order: a donor cj is drawn with probability proportional
+ *       to max(count_j - 1, 0) over the running counts, c[ci] = c[cj], then for even j c[ci][j] *= 1 + 1/1024 and
+ *       c[cj][j] *= 1 - 1/1024 (odd j: the factors swapped), and the donor's running count is halved between the two.
+ *       This is faiss's algorithm, NOT faiss's random stream: the draw is a counter-based hash of (seed, iteration, ci),
+ *       so the same arguments give the same split, with no state anywhere.
+ *     flags: KP2D_VPR_FP32; KP2D_KMEANS_SPHERICAL (every centroid L2-normalised after the update, faiss spherical=True);
+ *       KP2D_KMEANS_NO_SPLIT (empty clusters keep their input centroid).
+ *   kp2d_kmeans_train: niter steps (iteration = 0 .. niter - 1) from centroids (in: initial, out: final), ping-ponging
+ *     two centroid buffers inside scratch; obj [niter].  assign / dist / counts are the last iteration's, i.e. against
+ *     the centroids BEFORE the final update, exactly what faiss's loop leaves.
+ *   dim: the index's rule (dim % 16 == 0, 16 <= dim <= 16384), else KP2D_ERR_UNSUPPORTED.  1 <= k <= 65536, n >= k,
+ *     niter >= 1, else KP2D_ERR_ARG; n < 2^31.  scratch: kp2d_kmeans_scratch_bytes(n, dim, k) bytes (0: bad shape); x,
+ *     centroids and scratch 16-byte aligned.
+ *   Determinism: no float atomics.  Each cluster's rows are listed in ascending point order by a stable counting sort
+ *     and summed in a fixed order: lists are cut into chunks of 512 rows, a chunk is summed by one wave (8 accumulators
+ *     per lane, a lane group count that depends on dim alone, fixed trees) and the chunk sums are added in chunk order.
+ *     Every size involved is a constant or a function of (n, k, dim), and the search is deterministic (above), so all
+ *     outputs are bit-identical across runs, devices of the same kind and however the work is sliced; kp2d_kmeans_train
+ *     equals niter calls of kp2d_kmeans_step.
+ *   Accuracy (u = 2^-24): assign and dist carry the search's contract with k = 1.  Given the assignment, a centroid
+ *     component is within 32 u mean_i |x_i| + 2 u |c64| of the float64 mean of the same rows (mean over the cluster's
+ *     rows of that component's magnitude); obj is within sum_i 34 u d64_i + 32 u obj64 of the float64 objective
+ *     (tests/kmeans_ref.py, pinned from both sides in tests/test_kmeans_cpu.py). */
+#define KP2D_KMEANS_SPHERICAL 2u
+#define KP2D_KMEANS_NO_SPLIT 4u
+size_t kp2d_kmeans_scratch_bytes(int64_t n, int dim, int k);
+int kp2d_kmeans_step(const float* x, int64_t n, int dim, const float* centroids_in, int k, uint32_t flags, uint64_t seed,
+                     int iteration, float* centroids_out, int64_t* assign, float* dist, int64_t* counts, float* obj,
+                     void* scratch, size_t scratch_bytes, void* stream);
+int kp2d_kmeans_train(const float* x, int64_t n, int dim, float* centroids /* in: initial, out: final */, int k, int niter,
+                      uint32_t flags, uint64_t seed, float* obj /* [niter] */, int64_t* assign, float* dist,
+                      int64_t* counts, void* scratch, size_t scratch_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

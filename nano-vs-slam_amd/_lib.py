@@ -111,6 +111,11 @@ SIGNATURES = {
     "kp2d_vpr_pack": (C.c_int, [_P, C.c_int64, C.c_int, _P, _P]),
     "kp2d_vpr_scratch_bytes": (C.c_size_t, [C.c_int, C.c_int64, C.c_int, C.c_int]),
     "kp2d_vpr_search": (C.c_int, [_P, _P, C.c_int64, C.c_int, _P, C.c_int, _P, C.c_int, C.c_uint32, _P, _P, _P, C.c_size_t, _P]),
+    "kp2d_kmeans_scratch_bytes": (C.c_size_t, [C.c_int64, C.c_int, C.c_int]),
+    "kp2d_kmeans_step": (C.c_int, [_P, C.c_int64, C.c_int, _P, C.c_int, C.c_uint32, C.c_uint64, C.c_int, _P, _P, _P, _P, _P, _P,
+                                   C.c_size_t, _P]),
+    "kp2d_kmeans_train": (C.c_int, [_P, C.c_int64, C.c_int, _P, C.c_int, C.c_int, C.c_uint32, C.c_uint64, _P, _P, _P, _P, _P,
+                                    C.c_size_t, _P]),
     # include/kp2d_lightglue.h
     "kp2d_lg_create": (C.c_int, [C.POINTER(Kp2dLgConfig), C.POINTER(_P)]),
     "kp2d_lg_destroy": (None, [_P]),

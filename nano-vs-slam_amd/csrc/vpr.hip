@@ -112,6 +112,9 @@ __global__ __launch_bounds__(256) void vpr_pack_kernel(const float* __restrict__
   }
 }
 
+// what the upper half of the last chunk reads when dim is 16 mod 32: zeros add nothing to any product
+__device__ __attribute__((aligned(16))) const unsigned char vpr_zero16[16] = {0};
+
 // one LDS buffer <- chunk `ch` of the tile's 128 database rows and the workgroup's 64 queries.  LDS image: row-major,
 // 128 B per row, the 16-B slot t of row r holding piece t ^ (r & 7) (the XOR swizzle sits on the global address, the
 // LDS image stays lane-linear for global_load_lds).  Split pieces 0-3: hi, 4-7: lo; fp32 pieces: 4 floats each.
@@ -121,6 +124,8 @@ __device__ inline void issue_chunk(unsigned char* stage, const VprSearchArgs& a,
   const size_t rb = row_bytes(a.dim);
   const size_t poff = F32 ? (size_t)ch * CHB + piece * 16
                           : 16 + (piece < 4 ? (size_t)ch * 64 + piece * 16 : (size_t)a.dim * 2 + ch * 64 + (piece - 4) * 16);
+  // elements 16 .. 31 of a chunk that ends past dim (fp32: pieces 4-7; split: pieces 2, 3 of hi and of lo) do not exist
+  const bool dead = (ch + 1) * KC > a.dim && (F32 ? piece >= 4 : (piece & 3) >= 2);
 #pragma unroll
   for (int i = 0; i < 6; ++i) {
     const int g = wave * 6 + i;               // 24 wave instructions of 1 KB: 16 for the rows, 8 for the queries
@@ -134,7 +139,7 @@ __device__ inline void issue_chunk(unsigned char* stage, const VprSearchArgs& a,
       if (qq >= a.nq) qq = a.nq - 1;
       src = F32 ? reinterpret_cast<const unsigned char*>(a.q + (int64_t)qq * a.dim) : a.qp + (int64_t)qq * rb;
     }
-    glds16(src + poff, stage + g * 1024);     // (the hardware adds lane * 16 to the wave-uniform LDS base)
+    glds16(dead ? vpr_zero16 : src + poff, stage + g * 1024);   // (the hardware adds lane * 16 to the wave-uniform LDS base)
   }
 }
 
@@ -184,7 +189,7 @@ template <bool F32>
 __device__ inline void tile_products(unsigned char* smem, const VprSearchArgs& a, int64_t r0, int q0, int wave, int lane,
                                      vf16 (&acc)[2]) {
   const int j = lane & 31, h = lane >> 5, wq = wave >> 1, wr = wave & 1;
-  const int nk = a.dim / KC;
+  const int nk = (a.dim + KC - 1) / KC;
   issue_chunk<F32>(smem, a, r0, q0, 0, wave, lane);
   for (int c = 0; c < nk; ++c) {
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");

@@ -265,7 +265,26 @@ class _NetVLAD(_Holder):
 
     def init_params(self, clsts, traindescs):
         """NetVLAD.init_params, vladv2=False (reference aggregators/netvlad.py:41-56): soft-assignment weights are the
-        unit-norm cluster centres scaled by alpha, alpha chosen so the runner-up cluster gets weight 0.01."""
+        unit-norm cluster centres scaled by alpha, alpha chosen so the runner-up cluster gets weight 0.01.
+        Two device tensors (clustering.get_clusters returns them) are handled on the device: |x - c|^2 = |x|^2 + 1 - 2 x.c
+        for a unit c, so the two largest dots of a descriptor belong to its two nearest unit centres and their
+        difference is half the gap of the two squared distances, which the flat index's top-2 gives directly."""
+        if isinstance(clsts, torch.Tensor) and isinstance(traindescs, torch.Tensor):
+            if clsts.device.type != "cuda" or traindescs.device.type != "cuda":
+                raise RuntimeError("init_params: CPU tensors are not supported (no CPU fallback); pass numpy or device tensors")
+            import math
+            from ...vpr import FlatL2Index
+            clsts = clsts.detach().to(torch.float32).contiguous()
+            unit = clsts / clsts.norm(dim=1, keepdim=True)
+            index = FlatL2Index(clsts.shape[1], device=clsts.device)
+            index.add(unit)
+            D, _ = index.search(traindescs.detach().to(clsts.device), 2)
+            self.alpha = (-math.log(0.01) / ((D[:, 1] - D[:, 0]) * 0.5).mean()).item()
+            dev = self.centroids.device
+            self.centroids = nn.Parameter(clsts.clone().to(dev))
+            self.conv.weight = nn.Parameter((self.alpha * unit).unsqueeze(2).unsqueeze(3).to(dev))
+            self.conv.bias = None
+            return
         import numpy as np
         unit = clsts / np.linalg.norm(clsts, axis=1, keepdims=True)
         dots = np.sort(np.dot(unit, traindescs.T), axis=0)[::-1, :]          # per descriptor, descending
