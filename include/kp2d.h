@@ -350,6 +350,73 @@ int kp2d_kmeans_train(const float* x, int64_t n, int dim, float* centroids /* in
                       uint32_t flags, uint64_t seed, float* obj /* [niter] */, int64_t* assign, float* dist,
                       int64_t* counts, void* scratch, size_t scratch_bytes, void* stream);
 
+/* ---- Scores of the dense heads: segmentation counts and depth sums (nano-vs-slam_amd/csrc/dense_metrics.hip) -----
+ * Replace what the reference's evaluate_segmentation takes from segmentation_models_pytorch (smp.metrics.get_stats,
+ * src/evaluation/segmentation.py:42-48) and the reductions inside its compute_errors_torch
+ * (src/evaluation/depth_estimation.py:58-83).  Stateless like kp2d_vpr_* and kp2d_kmeans_*: caller-owned device buffers,
+ * the caller's stream, no synchronisation and no host round trip; every output is zeroed or fully written by the call
+ * itself; arguments are checked before anything touches the device.  1 <= B <= 65535, n >= 1 elements per image.
+ *
+ * kp2d_seg_stats: per-image, per-class confusion counts.
+ *   pred [B,n] int64 (what post_processing leaves in out["seg"]); target [B,n] of target_dtype KP2D_SEG_U8 / _I32 / _I64;
+ *   1 <= num_classes = C <= 1024; ignore_index: any int64 except KP2D_SEG_NO_IGNORE, which means "ignore nothing".
+ *   stats [B,C,4] int64 = (tp, fp, fn, tn); confusion [B,C,C] int64 or NULL (row = target class, column = predicted
+ *   class; C <= 256, else KP2D_ERR_UNSUPPORTED); ignored [B] int64; stray [B] int64.
+ *   Counting rule (this text is the definition):
+ *     - a pixel whose target equals ignore_index is IGNORED: it adds to ignored[b] and to nothing else;
+ *     - a pixel that is not ignored but whose target or prediction lies outside [0, C) is STRAY: it adds to stray[b]
+ *       and to nothing else (valid data has none);
+ *     - every other pixel is COUNTED, with target g and prediction p: g == p: tp[g] += 1 and confusion[g][g] += 1;
+ *       otherwise fp[p] += 1, fn[g] += 1 and confusion[g][p] += 1;
+ *     - tn[c] = counted - tp[c] - fp[c] - fn[c], so the four add up to n - ignored[b] - stray[b] for every class.
+ *   With no stray pixel this is what smp.metrics.get_stats(mode="multiclass", ignore_index=...) returns.  That sentence
+ *   was restated from smp's definition; smp was not available to run against.
+ *   All counts are exact integers (integer LDS and global atomics only): outputs are bit-identical however the pixels are
+ *   cut over workgroups.  The confusion matrix is gathered in an LDS tile for C <= kp2d_seg_conf_lds_max() and with one
+ *   global add per pixel above it; the results do not differ.
+ *
+ * kp2d_depth_sums: the sums behind the nine depth metrics.
+ *   gt, pred [B,n] fp32; valid [B,n] uint8 or NULL; min_depth / max_depth: limits on gt, a NaN turns that limit off.
+ *   sums [B,KP2D_DEPTH_NSUMS] float64, per image: 0 count; 1-3 #(max(g/p, p/g) < 1.25, < 1.25^2, < 1.25^3);
+ *   4 sum |g-p|/g; 5 sum (g-p)^2/g; 6 sum (g-p)^2; 7 sum (ln g - ln p)^2; 8 sum (ln p - ln g); 9 sum |log10 g - log10 p|;
+ *   10 number of invalid pixels.  scratch: kp2d_depth_scratch_bytes(B, n) bytes (0: bad shape), 8-byte aligned; a shorter
+ *   one is KP2D_ERR_ARG.
+ *   Invalid-pixel rule: a pixel is invalid when gt or pred is non-finite or <= 0, or gt < min_depth, or gt > max_depth,
+ *   or valid is 0.  Invalid pixels enter no sum and are tallied in slot 10; count + invalid = n.  (The reference has no
+ *   such rule: one zero or NaN there poisons the mean of the whole batch.)
+ *   Arithmetic: inputs are widened to float64; every term and every sum is float64 (the call is bound by reading two
+ *   floats per pixel, the arithmetic is free).  The threshold counts use IEEE float64 division and equal numpy's float64
+ *   counts exactly; slots 0-3 and 10 are exact integers.
+ *   Determinism: no float atomics.  An image is cut into chunks of 4096 pixels; thread t of a chunk's 256 adds the terms
+ *   of pixels t, t + 256, ... in that order, lanes are combined by a butterfly and the four waves in wave order; the
+ *   chunk sums are then added the same way (thread t: chunks t, t + 256, ...).  The order depends on n alone, and no
+ *   image's sum meets another's: a row of sums is bit-identical from run to run and whether the image is evaluated alone
+ *   or inside a batch.
+ *   Accuracy (u = 2^-53).  A term takes part in at most D(n) = 33 + ceil(ceil(n / 4096) / 256) rounded additions (15 in
+ *   the thread, 6 + 3 in the workgroup, the same over the chunks), so a sum of exact terms is within D u sum|t_i|; on top
+ *   comes each term's own rounding.  L is the error of the device library's double log / log10 in ulp: its
+ *   documentation is not part of the installed ROCm tree, so L = 4 is an ASSUMPTION, not a documented figure.
+ *   Against the float64 value of the same fp32 inputs, with d = ln g - ln p and d10 = log10 g - log10 p:
+ *     slot 4: (D + 2) u sum |g-p|/g          slot 5: (D + 4) u sum (g-p)^2/g          slot 6: (D + 3) u sum (g-p)^2
+ *     slot 7: (D + 3 + 4 L) u sum [ d^2 + |d| (|ln g| + |ln p|) ]
+ *     slot 8: (D + 1 + 2 L) u sum [ |d| + |ln g| + |ln p| ]
+ *     slot 9: (D + 1 + 2 L) u sum [ |d10| + |log10 g| + |log10 p| ]
+ *   each times 1.001 for the second-order terms.  The log slots pay for the cancellation in ln g - ln p: each logarithm
+ *   is wrong by up to 2 L u |ln x|, whatever is left of it in the difference.  tests/dense_ref.py restates these bounds;
+ *   tests/test_dense_metrics_cpu.py checks that they hold for float64 sums in other orders, that one term evaluated in
+ *   float32 breaks them, and that they stay below 2^-40 sum|t_i| on the test inputs. */
+#define KP2D_SEG_U8 0
+#define KP2D_SEG_I32 1
+#define KP2D_SEG_I64 2
+#define KP2D_SEG_NO_IGNORE INT64_MIN
+#define KP2D_DEPTH_NSUMS 11
+int kp2d_seg_conf_lds_max(void);
+int kp2d_seg_stats(const int64_t* pred, const void* target, int target_dtype, int B, int64_t n, int num_classes,
+                   int64_t ignore_index, int64_t* stats, int64_t* confusion, int64_t* ignored, int64_t* stray, void* stream);
+size_t kp2d_depth_scratch_bytes(int B, int64_t n);
+int kp2d_depth_sums(const float* gt, const float* pred, const uint8_t* valid, int B, int64_t n, double min_depth,
+                    double max_depth, double* sums, void* scratch, size_t scratch_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -116,6 +116,10 @@ SIGNATURES = {
                                    C.c_size_t, _P]),
     "kp2d_kmeans_train": (C.c_int, [_P, C.c_int64, C.c_int, _P, C.c_int, C.c_int, C.c_uint32, C.c_uint64, _P, _P, _P, _P, _P,
                                     C.c_size_t, _P]),
+    "kp2d_seg_conf_lds_max": (C.c_int, []),
+    "kp2d_seg_stats": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int64, C.c_int, C.c_int64, _P, _P, _P, _P, _P]),
+    "kp2d_depth_scratch_bytes": (C.c_size_t, [C.c_int, C.c_int64]),
+    "kp2d_depth_sums": (C.c_int, [_P, _P, _P, C.c_int, C.c_int64, C.c_double, C.c_double, _P, _P, C.c_size_t, _P]),
     # include/kp2d_lightglue.h
     "kp2d_lg_create": (C.c_int, [C.POINTER(Kp2dLgConfig), C.POINTER(_P)]),
     "kp2d_lg_destroy": (None, [_P]),
