@@ -417,6 +417,60 @@ size_t kp2d_depth_scratch_bytes(int B, int64_t n);
 int kp2d_depth_sums(const float* gt, const float* pred, const uint8_t* valid, int B, int64_t n, double min_depth,
                     double max_depth, double* sums, void* scratch, size_t scratch_bytes, void* stream);
 
+/* ---- Keypoint scores: repeatability, localisation error, matching score (nano-vs-slam_amd/csrc/keypoint_metrics.hip) ----
+ * The counts and sums behind the reference's compute_repeatability (src/evaluation/detector.py:67-113) and
+ * compute_matching_score (src/evaluation/descriptor.py:112-170), for B image pairs per call.  Stateless like the calls
+ * above: caller-owned device buffers, the caller's stream, no synchronisation, no host round trip; every output is fully
+ * written by the call; arguments are checked before anything touches the device (bad shapes: KP2D_ERR_ARG).  The homography
+ * fit (compute_homography: mutual matches + RANSAC) and the correctness / AUC values built on it are NOT part of this.
+ *   pts0 [B,k0,3], pts1 [B,k1,3] fp32 rows (x, y, probability) of image 0 / image 1; cnt0, cnt1 [B] int32 rows that exist
+ *   (clamped to [0, k]; the rest is padding and never read).  k0, k1 in [0, 65536] (a set may be empty: pts may then be
+ *   NULL), 1 <= B <= 65535, keep_k >= 1.  hom [B,9] float64, row-major: maps image-0 pixels to image-1 pixels.
+ *   scratch: kp2d_kp_scratch_bytes(B, k0, k1, C, keep_k) bytes (C = 0: repeatability only; 0 is returned for a bad shape),
+ *   16-byte aligned; a shorter one is KP2D_ERR_ARG.
+ *   Arithmetic: every coordinate is widened to float64 and all geometry is float64, as in the reference (its numpy code is
+ *   float64 because warp_keypoints appends a float64 column of ones).  inv(hom) is the adjugate over the determinant in
+ *   float64; the reference calls np.linalg.inv; the two agree to rounding.
+ *   Selection ("the keep_k most probable rows"): row i ranks before row j when its probability is greater, or equal and
+ *   i < j: among equal probabilities the LOWER row index is kept (numpy's argsort is unstable, so the reference defines no
+ *   order there).  -0 and +0 are equal; probabilities are expected not to be NaN.
+ *   The box quirk: the box test is 0 <= x < b0 and 0 <= y < b1, and the reference passes image_shape = (H, W) as (b0, b1):
+ *   x is compared with the HEIGHT and y with the WIDTH (detector.py:41-46, keypoints.py:133).  Reproduced as is; pass the
+ *   bounds the way the reference does to get its numbers.
+ *
+ * kp2d_kp_repeatability: set 1 keeps the rows whose warp by inv(hom) lies in the box; set 0 is warped by hom and keeps the
+ *   rows whose warped point lies in the box; of each surviving set the keep_k most probable rows go on (N1 of set 0, N2 of
+ *   set 1); every row's distance to the nearest row of the other set is taken in both directions, between the WARPED
+ *   points of set 0 and the points of set 1.  counts [B,4] int64 = (N1, N2, count1, count2): count1 = rows of set 0 whose
+ *   nearest distance is <= distance_thresh (NON-strict), count2 the same for set 1; le [B,2] float64 = (le1, le2), the sums
+ *   of those distances.  An empty other set gives count = 0 and le = 0.  repeatability = (count1 + count2) / (N1 + N2) and
+ *   loc_err = (le1 + le2) / (count1 + count2) are the caller's two divisions.
+ *   Determinism: no float atomics.  The selected rows of a set are ordered by rank; thread t of a pair's workgroup adds the
+ *   distances of ranks t, t + 256, ... in that order and the 256 partial sums are added by a fixed binary tree, so the order
+ *   depends on the row ranks alone: outputs are bit-identical from run to run and whether a pair is scored alone or inside
+ *   a batch, with any padding.
+ *   Accuracy: le sums n <= 2 keep_k float64 terms, each <= distance_thresh, each carrying a few roundings of its own; any
+ *   order of summation is within n^2 eps distance_thresh of the exact sum (eps = 2^-53): about 3e-10 at n = 1000 and
+ *   distance_thresh = 3, which is why le1 and le2 are compared with the reference at 1e-9 absolute.  The counts are exact
+ *   whenever no distance lies within rounding of distance_thresh and no warped coordinate within rounding of the box.
+ *
+ * kp2d_kp_matching_score: NO visibility filter (as in the reference): the keep_k most probable rows of each set, points and
+ *   descriptors (desc0 [B,k0,C], desc1 [B,k1,C] fp32, 16-byte aligned, C in {32, 64, 128}), are gathered and matched in
+ *   both directions by kp2d_match_descriptors_ex, whose nn_idx is cv2.BFMatcher(NORM_L2, crossCheck=False).match with the
+ *   tie rule stated there.  Direction 1: the match in set 1 of every selected row of set 0 is warped by inv(hom); it is
+ *   visible when 0 <= x <= b0 - 1 and 0 <= y <= b1 - 1, and correct when its distance to the row's own point is < 3
+ *   (STRICT, a constant of the reference; compare the non-strict <= distance_thresh above).  Direction 2: the match in
+ *   set 0 of every selected row of set 1, warped by hom.  counts [B,4] int64 = (vis1, hit1, vis2, hit2): visible matches and
+ *   visible-and-correct matches per direction; the score is (hit1 / max(vis1, 1) + hit2 / max(vis2, 1)) / 2.  Either set
+ *   empty: all four are 0 (the reference returns 0).  Integer counts: exact and order-free. */
+size_t kp2d_kp_scratch_bytes(int B, int k0, int k1, int C, int keep_k);
+int kp2d_kp_repeatability(const float* pts0, const int32_t* cnt0, const float* pts1, const int32_t* cnt1, const double* hom,
+                          int B, int k0, int k1, double b0, double b1, int keep_k, double distance_thresh, int64_t* counts,
+                          double* le, void* scratch, size_t scratch_bytes, void* stream);
+int kp2d_kp_matching_score(const float* pts0, const int32_t* cnt0, const float* desc0, const float* pts1, const int32_t* cnt1,
+                           const float* desc1, const double* hom, int B, int k0, int k1, int C, double b0, double b1,
+                           int keep_k, int64_t* counts, void* scratch, size_t scratch_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

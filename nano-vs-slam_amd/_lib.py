@@ -120,6 +120,10 @@ SIGNATURES = {
     "kp2d_seg_stats": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int64, C.c_int, C.c_int64, _P, _P, _P, _P, _P]),
     "kp2d_depth_scratch_bytes": (C.c_size_t, [C.c_int, C.c_int64]),
     "kp2d_depth_sums": (C.c_int, [_P, _P, _P, C.c_int, C.c_int64, C.c_double, C.c_double, _P, _P, C.c_size_t, _P]),
+    "kp2d_kp_scratch_bytes": (C.c_size_t, [C.c_int] * 5),
+    "kp2d_kp_repeatability": (C.c_int, [_P] * 5 + [C.c_int] * 3 + [C.c_double, C.c_double, C.c_int, C.c_double, _P, _P, _P, C.c_size_t,
+                                        _P]),
+    "kp2d_kp_matching_score": (C.c_int, [_P] * 7 + [C.c_int] * 4 + [C.c_double, C.c_double, C.c_int, _P, _P, C.c_size_t, _P]),
     # include/kp2d_lightglue.h
     "kp2d_lg_create": (C.c_int, [C.POINTER(Kp2dLgConfig), C.POINTER(_P)]),
     "kp2d_lg_destroy": (None, [_P]),

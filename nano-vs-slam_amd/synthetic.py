@@ -19,7 +19,7 @@ import zlib
 import numpy as np
 
 __all__ = ["spread_tensor", "spread_state_dict", "synthetic_frames", "seeded_linear_state_dict",
-           "trained_like_tensor", "trained_like_state_dict"]
+           "trained_like_tensor", "trained_like_state_dict", "random_homographies", "homography_pairs"]
 
 
 def _rng(seed: int, key: str) -> np.random.Generator:
@@ -124,6 +124,43 @@ def synthetic_frames(B: int, H: int, W: int, seed: int = 7, smooth: bool = False
                 acc += p[:, :, dy:dy + H, dx:dx + W]
         x = (acc / 9.0 * 2.5).clip(-1, 1).astype(np.float32)
     return x
+
+
+def random_homographies(B: int, H: int, W: int, seed: int = 7) -> np.ndarray:
+    """Seeded homographies [B,3,3] float64 in pixel coordinates (x along the width), image 0 -> image 1: rotation within
+    +-0.2 rad and scale in [0.9, 1.15] about the image centre, translation within +-8 % of the image size, perspective
+    terms within +-0.15 / size; the image centre stays inside the image."""
+    g = np.random.default_rng([seed, 0x486F6D])
+    c = np.array([[1, 0, (W - 1) / 2], [0, 1, (H - 1) / 2], [0, 0, 1.0]])
+    out = np.empty((B, 3, 3))
+    for b in range(B):
+        a, s = g.uniform(-0.2, 0.2), g.uniform(0.9, 1.15)
+        m = np.array([[s * np.cos(a), -s * np.sin(a), g.uniform(-0.08, 0.08) * W],
+                      [s * np.sin(a), s * np.cos(a), g.uniform(-0.08, 0.08) * H],
+                      [g.uniform(-0.15, 0.15) / W, g.uniform(-0.15, 0.15) / H, 1.0]])
+        out[b] = c @ m @ np.linalg.inv(c)
+    return out
+
+
+def homography_pairs(B: int, H: int, W: int, seed: int = 7, smooth: bool = True, device="cuda", identity: bool = False):
+    """Seeded image pairs related by a known homography, for the keypoint scores (keypoint_metrics.py): -> (frames
+    [B,3,H,W] float32, homography [B,3,3] float64, warped [B,3,H,W] float32), torch tensors on ``device``.  ``frames`` are
+    synthetic_frames; ``warped[b]`` shows ``frames[b]`` through ``homography[b]`` (image-0 pixels -> image-1 pixels): every
+    pixel of the second image samples the first at inv(homography) of its position, bilinear, zeros outside, by a plain
+    torch.nn.functional.grid_sample on the device.  ``identity``: unit homographies, and ``warped`` is ``frames`` itself."""
+    import torch
+    frames = torch.from_numpy(synthetic_frames(B, H, W, seed, smooth)).to(device)
+    if identity:
+        return frames, torch.eye(3, dtype=torch.float64, device=device).repeat(B, 1, 1), frames.clone()
+    hom = torch.from_numpy(random_homographies(B, H, W, seed)).to(device)
+    ys, xs = torch.meshgrid(torch.arange(H, dtype=torch.float64, device=device), torch.arange(W, dtype=torch.float64, device=device),
+                            indexing="ij")
+    p1 = torch.stack([xs, ys, torch.ones_like(xs)], 0).reshape(3, -1)                       # pixels of the second image
+    p0 = torch.linalg.inv(hom) @ p1                                                         # where each comes from
+    x0, y0 = p0[:, 0] / p0[:, 2], p0[:, 1] / p0[:, 2]
+    grid = torch.stack([2.0 * x0 / (W - 1) - 1.0, 2.0 * y0 / (H - 1) - 1.0], -1).reshape(B, H, W, 2).to(torch.float32)
+    warped = torch.nn.functional.grid_sample(frames, grid, mode="bilinear", padding_mode="zeros", align_corners=True)
+    return frames, hom, warped
 
 
 def seeded_linear_state_dict(shapes: dict, seed: int = 4321) -> dict:
