@@ -10,15 +10,15 @@ There is no CPU path: CPU tensors raise, like the rest of the product.
 """
 from __future__ import annotations
 
-import ctypes as C
 import warnings
 from math import ceil
 
 import numpy as np
 import torch
 
-from . import _lib
-from .vpr import PRECISIONS, FlatL2Index, _ptr, check_dim
+from . import _dev, _lib
+from ._dev import ptr as _ptr, stream as _stream
+from .vpr import PRECISIONS, FlatL2Index, check_dim
 
 KMEANS_SPHERICAL = 2
 KMEANS_NO_SPLIT = 4
@@ -39,7 +39,7 @@ def _outputs(x, centroids, nobj):
     nbytes = int(lib.kp2d_kmeans_scratch_bytes(n, x.shape[1], k))
     return (lib, torch.empty(nobj, dtype=torch.float32, device=dev), torch.empty(n, dtype=torch.int64, device=dev),
             torch.empty(n, dtype=torch.float32, device=dev), torch.empty(k, dtype=torch.int64, device=dev),
-            torch.empty(max(nbytes, 256), dtype=torch.uint8, device=dev), C.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
+            _dev.scratch(nbytes, dev), _stream(dev))
 
 
 def kmeans_step(x, centroids, flags=0, seed=1234, iteration=0):
@@ -99,8 +99,7 @@ class Kmeans:
         if isinstance(x, np.ndarray):
             is_np = True
         elif isinstance(x, torch.Tensor):
-            if x.device.type != "cuda":
-                raise RuntimeError(f"{what}: CPU tensors are not supported (no CPU fallback); pass numpy or a device tensor")
+            _dev.require_device(what, x, "pass numpy or a device tensor")
             is_np = False
         else:
             raise TypeError(f"{what} must be a numpy array or a torch tensor")

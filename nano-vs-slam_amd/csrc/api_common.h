@@ -24,6 +24,22 @@ inline int fail(int code, const char* fmt, ...) {
 constexpr size_t ALIGN = 256;
 inline size_t align_up(size_t v, size_t a = ALIGN) { return (v + a - 1) / a * a; }
 
+// One walk defines a scratch layout: a feature's layout function takes its pieces in order and returns typed pointers.
+// base == nullptr is the sizing pass (every pointer null, bytes() the size); with the caller's buffer the same walk
+// yields the pointers.  A piece starts at align_up(end, align); the layout's owner decides how bytes() is rounded.
+struct Carve {
+  char* base = nullptr;
+  size_t end = 0;
+  explicit Carve(void* scratch = nullptr) : base(static_cast<char*>(scratch)) {}
+  template <class T>
+  T* take(size_t count, size_t align = ALIGN) {
+    const size_t at = align_up(end, align);
+    end = at + count * sizeof(T);
+    return base ? reinterpret_cast<T*>(base + at) : nullptr;
+  }
+  size_t bytes(size_t align = ALIGN) const { return align_up(end, align); }
+};
+
 }  // namespace kp2d
 
 #define HIP_TRY(expr)                                                                                \

@@ -266,40 +266,45 @@ __global__ __launch_bounds__(WG) void kp_score_kernel(const KpSets a, const int3
   }
 }
 
-// scratch layout; C = 0: repeatability only
-struct KpLayout {
-  size_t keys[2], wp[2], cp[2], src[2], nsel, dc[2], nn[2], nd, nd2, mq, md, match, match_bytes, total;
-  int kk[2];
+// scratch layout, every piece on an ALIGN boundary: one walk fills the selection's buffers (a.keys / wp / cp / nsel, kk) and,
+// for the matching score (C > 0), the compact rows, the descriptors gathered by them and the matcher's outputs and scratch.
+// C = 0: repeatability only.
+struct KpScratch {
+  int32_t* nn[2];             // [B,kk] nearest row of the other set, per direction
+  float* nd; float* nd2; int32_t* mq; float* md;      // the matcher's other outputs (not read): [B, max kk]
+  void* match; size_t match_bytes;                     // its scratch, for the larger direction
+  size_t bytes;
 };
 
-KpLayout kp_layout(int B, int k0, int k1, int C, int keep_k) {
-  KpLayout L{};
-  const int k[2] = {k0, k1};
-  size_t off = 0;
-  auto take = [&](size_t bytes) { const size_t o = off; off += align_up(bytes); return o; };
+KpScratch kp_layout(void* scratch, int B, int k0, int k1, int C, int keep_k, KpSets& a, KpGather& g) {
+  Carve c(scratch);
+  KpScratch w{};
+  a.B = B;
+  a.k[0] = k0; a.k[1] = k1;
   for (int s = 0; s < 2; ++s) {
-    L.kk[s] = std::min(keep_k, k[s]);
-    L.keys[s] = take((size_t)B * k[s] * sizeof(u64));
-    L.wp[s] = take((size_t)B * k[s] * sizeof(double2));
-    L.cp[s] = take((size_t)B * L.kk[s] * sizeof(double2));
+    a.kk[s] = std::min(keep_k, a.k[s]);
+    a.keys[s] = c.take<u64>((size_t)B * a.k[s]);
+    a.wp[s] = c.take<double2>((size_t)B * a.k[s]);
+    a.cp[s] = c.take<double2>((size_t)B * a.kk[s]);
   }
-  L.nsel = take((size_t)2 * B * sizeof(int32_t));
+  a.nsel = c.take<int32_t>((size_t)2 * B);
   if (C > 0) {
-    const size_t km = (size_t)std::max(L.kk[0], L.kk[1]);
+    const size_t km = (size_t)std::max(a.kk[0], a.kk[1]);
+    g.C = C;
     for (int s = 0; s < 2; ++s) {
-      L.src[s] = take((size_t)B * L.kk[s] * sizeof(int32_t));
-      L.dc[s] = take((size_t)B * L.kk[s] * C * sizeof(float));
-      L.nn[s] = take((size_t)B * L.kk[s] * sizeof(int32_t));
+      a.src[s] = c.take<int32_t>((size_t)B * a.kk[s]);
+      g.out[s] = c.take<float>((size_t)B * a.kk[s] * C);
+      w.nn[s] = c.take<int32_t>((size_t)B * a.kk[s]);
     }
-    L.nd = take(B * km * sizeof(float));
-    L.nd2 = take(B * km * sizeof(float));
-    L.mq = take(B * km * sizeof(int32_t));
-    L.md = take(B * km * sizeof(float));
-    L.match_bytes = std::max(kp2d_match_scratch_bytes(B, L.kk[0], L.kk[1]), kp2d_match_scratch_bytes(B, L.kk[1], L.kk[0]));
-    L.match = take(L.match_bytes);
+    w.nd = c.take<float>(B * km);
+    w.nd2 = c.take<float>(B * km);
+    w.mq = c.take<int32_t>(B * km);
+    w.md = c.take<float>(B * km);
+    w.match_bytes = std::max(kp2d_match_scratch_bytes(B, a.kk[0], a.kk[1]), kp2d_match_scratch_bytes(B, a.kk[1], a.kk[0]));
+    w.match = c.take<char>(w.match_bytes);
   }
-  L.total = std::max(off, ALIGN);
-  return L;
+  w.bytes = std::max(c.bytes(), ALIGN);
+  return w;
 }
 
 int check_shape(const char* who, int B, int k0, int k1, int keep_k) {
@@ -324,27 +329,6 @@ int check_common(const char* who, const float* pts0, const int32_t* cnt0, const 
   return KP2D_OK;
 }
 
-KpSets make_sets(const KpLayout& L, const float* pts0, const int32_t* cnt0, const float* pts1, const int32_t* cnt1,
-                 const double* hom, int B, int k0, int k1, double b0, double b1, int keep_k, void* scratch, bool want_src) {
-  char* base = reinterpret_cast<char*>(scratch);
-  KpSets a{};
-  a.pts[0] = pts0; a.pts[1] = pts1;
-  a.cnt[0] = cnt0; a.cnt[1] = cnt1;
-  a.k[0] = k0; a.k[1] = k1;
-  for (int s = 0; s < 2; ++s) {
-    a.kk[s] = L.kk[s];
-    a.keys[s] = reinterpret_cast<u64*>(base + L.keys[s]);
-    a.wp[s] = reinterpret_cast<double2*>(base + L.wp[s]);
-    a.cp[s] = reinterpret_cast<double2*>(base + L.cp[s]);
-    a.src[s] = want_src ? reinterpret_cast<int32_t*>(base + L.src[s]) : nullptr;
-  }
-  a.nsel = reinterpret_cast<int32_t*>(base + L.nsel);
-  a.hom = hom;
-  a.B = B;
-  a.b0 = b0; a.b1 = b1;
-  return a;
-}
-
 template <bool BOX>
 int launch_select(const KpSets& a, hipStream_t st) {
   const unsigned gx = (unsigned)std::max(1, (std::max(a.k[0], a.k[1]) + WG - 1) / WG);
@@ -360,7 +344,9 @@ extern "C" {
 size_t kp2d_kp_scratch_bytes(int B, int k0, int k1, int C, int keep_k) {
   if (B < 1 || B > MAX_B || k0 < 0 || k0 > MAX_K || k1 < 0 || k1 > MAX_K || keep_k < 1) return 0;
   if (C != 0 && C != 32 && C != 64 && C != 128) return 0;
-  return kp_layout(B, k0, k1, C, keep_k).total;
+  KpSets a{};
+  KpGather g{};
+  return kp_layout(nullptr, B, k0, k1, C, keep_k, a, g).bytes;
 }
 
 int kp2d_kp_repeatability(const float* pts0, const int32_t* cnt0, const float* pts1, const int32_t* cnt1, const double* hom,
@@ -368,13 +354,15 @@ int kp2d_kp_repeatability(const float* pts0, const int32_t* cnt0, const float* p
                           double* le, void* scratch, size_t scratch_bytes, void* stream) {
   if (int e = check_shape("kp_repeatability", B, k0, k1, keep_k)) return e;
   if (std::isnan(distance_thresh)) return fail(KP2D_ERR_ARG, "kp_repeatability: distance_thresh is NaN");
-  const KpLayout L = kp_layout(B, k0, k1, 0, keep_k);
-  if (int e = check_common("kp_repeatability", pts0, cnt0, pts1, cnt1, hom, k0, k1, b0, b1, counts, scratch, scratch_bytes, L.total))
+  KpSets a{{pts0, pts1}, {cnt0, cnt1}};
+  a.hom = hom; a.b0 = b0; a.b1 = b1;
+  KpGather g{};
+  const KpScratch w = kp_layout(scratch, B, k0, k1, 0, keep_k, a, g);
+  if (int e = check_common("kp_repeatability", pts0, cnt0, pts1, cnt1, hom, k0, k1, b0, b1, counts, scratch, scratch_bytes, w.bytes))
     return e;
   if (!le || (uintptr_t)le % 8) return fail(KP2D_ERR_ARG, "kp_repeatability: le is null or misaligned");
   hipStream_t st = (hipStream_t)stream;
   DeviceGuard guard(hom, st);
-  const KpSets a = make_sets(L, pts0, cnt0, pts1, cnt1, hom, B, k0, k1, b0, b1, keep_k, scratch, false);
   if (int e = launch_select<true>(a, st)) return fail(KP2D_ERR_HIP, "kp_repeatability: selection kernels: %d", e);
   hipLaunchKernelGGL(kp_nearest_kernel, dim3(B, 2), dim3(WG), 0, st, a, distance_thresh, counts, le);
   HIP_TRY(hipGetLastError());
@@ -386,8 +374,12 @@ int kp2d_kp_matching_score(const float* pts0, const int32_t* cnt0, const float* 
                            int keep_k, int64_t* counts, void* scratch, size_t scratch_bytes, void* stream) {
   if (int e = check_shape("kp_matching_score", B, k0, k1, keep_k)) return e;
   if (C != 32 && C != 64 && C != 128) return fail(KP2D_ERR_ARG, "kp_matching_score: descriptor width %d (32, 64 or 128)", C);
-  const KpLayout L = kp_layout(B, k0, k1, C, keep_k);
-  if (int e = check_common("kp_matching_score", pts0, cnt0, pts1, cnt1, hom, k0, k1, b0, b1, counts, scratch, scratch_bytes, L.total))
+  KpSets a{{pts0, pts1}, {cnt0, cnt1}};
+  a.hom = hom; a.b0 = b0; a.b1 = b1;
+  KpGather g{};
+  g.desc[0] = desc0; g.desc[1] = desc1;
+  const KpScratch w = kp_layout(scratch, B, k0, k1, C, keep_k, a, g);
+  if (int e = check_common("kp_matching_score", pts0, cnt0, pts1, cnt1, hom, k0, k1, b0, b1, counts, scratch, scratch_bytes, w.bytes))
     return e;
   if ((k0 > 0 && !desc0) || (k1 > 0 && !desc1)) return fail(KP2D_ERR_ARG, "kp_matching_score: null descriptors");
   if ((uintptr_t)desc0 % 16 || (uintptr_t)desc1 % 16) return fail(KP2D_ERR_ARG, "kp_matching_score: descriptors must be 16-byte aligned");
@@ -397,28 +389,16 @@ int kp2d_kp_matching_score(const float* pts0, const int32_t* cnt0, const float* 
     HIP_TRY(hipMemsetAsync(counts, 0, (size_t)B * 4 * sizeof(int64_t), st));
     return KP2D_OK;
   }
-  const KpSets a = make_sets(L, pts0, cnt0, pts1, cnt1, hom, B, k0, k1, b0, b1, keep_k, scratch, true);
   if (int e = launch_select<false>(a, st)) return fail(KP2D_ERR_HIP, "kp_matching_score: selection kernels: %d", e);
-  char* base = reinterpret_cast<char*>(scratch);
-  KpGather g{};
-  g.desc[0] = desc0; g.desc[1] = desc1;
-  g.out[0] = reinterpret_cast<float*>(base + L.dc[0]);
-  g.out[1] = reinterpret_cast<float*>(base + L.dc[1]);
-  g.C = C;
-  const int kmax = std::max(L.kk[0], L.kk[1]);
+  const int kmax = std::max(a.kk[0], a.kk[1]);
   hipLaunchKernelGGL(kp_gather_kernel, dim3((unsigned)(((size_t)kmax * (C / 4) + WG - 1) / WG), B, 2), dim3(WG), 0, st, a, g);
   HIP_TRY(hipGetLastError());
-  int32_t* nn[2] = {reinterpret_cast<int32_t*>(base + L.nn[0]), reinterpret_cast<int32_t*>(base + L.nn[1])};
-  float* nd = reinterpret_cast<float*>(base + L.nd);
-  float* nd2 = reinterpret_cast<float*>(base + L.nd2);
-  int32_t* mq = reinterpret_cast<int32_t*>(base + L.mq);
-  float* md = reinterpret_cast<float*>(base + L.md);
   // cv2.BFMatcher(NORM_L2, crossCheck=False).match in both directions: nn_idx is all that is read
   for (int d = 0; d < 2; ++d)
-    if (int e = kp2d_match_descriptors_ex(g.out[d], a.nsel + d * B, g.out[1 - d], a.nsel + (1 - d) * B, B, L.kk[d], L.kk[1 - d], C,
-                                          0.7f, nullptr, nullptr, 0u, nn[d], nd, nd2, mq, md, base + L.match, L.match_bytes, stream))
+    if (int e = kp2d_match_descriptors_ex(g.out[d], a.nsel + d * B, g.out[1 - d], a.nsel + (1 - d) * B, B, a.kk[d], a.kk[1 - d], C,
+                                          0.7f, nullptr, nullptr, 0u, w.nn[d], w.nd, w.nd2, w.mq, w.md, w.match, w.match_bytes, stream))
       return e;
-  hipLaunchKernelGGL(kp_score_kernel, dim3(B, 2), dim3(WG), 0, st, a, nn[0], nn[1], counts);
+  hipLaunchKernelGGL(kp_score_kernel, dim3(B, 2), dim3(WG), 0, st, a, w.nn[0], w.nn[1], counts);
   HIP_TRY(hipGetLastError());
   return KP2D_OK;
 }

@@ -45,14 +45,18 @@ constexpr int MIN_SLAB = 256;               // rows per slab at least
 constexpr int64_t HIST_CELLS = 1 << 22;     // slabs x k at most (16 MB of histograms), unless k alone exceeds it
 constexpr float SPLIT_EPS = 1.f / 1024.f;
 
+// the slicing of a step and its scratch (with the two centroid buffers kp2d_kmeans_train alternates between), as one walk:
+// every piece on an ALIGN boundary.  scratch == nullptr: the sizing pass
 struct KmPlan {
   int nslab;
   int64_t slab, nwork;
-  size_t off_cpack, off_vpr, off_hist, off_start, off_cstart, off_rcount, off_elist, off_meta, off_order, off_part, off_c0, off_c1,
-      total;
+  unsigned char *cpack, *vpr;      // the centroids packed as a vpr database; the search's own scratch
+  int *hist, *start, *cstart, *rcount, *elist, *meta, *order;
+  float *part, *c0, *c1;
+  size_t total;
 };
 
-KmPlan km_plan(int64_t n, int dim, int k) {
+KmPlan km_plan(void* scratch, int64_t n, int dim, int k) {
   KmPlan p{};
   const int64_t by_rows = (n + MIN_SLAB - 1) / MIN_SLAB, by_cells = std::max<int64_t>(1, HIST_CELLS / k);
   p.nslab = (int)std::max<int64_t>(1, std::min(by_rows, by_cells));
@@ -60,23 +64,22 @@ KmPlan km_plan(int64_t n, int dim, int k) {
   p.nslab = (int)((n + p.slab - 1) / p.slab);
   p.nwork = (n + CHUNK - 1) / CHUNK + k;    // sum_c ceil(count_c / CHUNK) never exceeds it
   const int64_t q0 = std::min<int64_t>(n, QCHUNK), q1 = n % QCHUNK;
-  size_t vs = vpr_plan((int)q0, k, dim, 1).total;
-  if (q1 > 0) vs = std::max(vs, vpr_plan((int)q1, k, dim, 1).total);
-  size_t o = 0;
-  auto take = [&](size_t bytes) { const size_t at = o; o = align_up(o + bytes); return at; };
-  p.off_cpack = take((size_t)k * vpr_row_bytes(dim));
-  p.off_vpr = take(vs);
-  p.off_hist = take((size_t)p.nslab * k * 4);
-  p.off_start = take((size_t)(k + 1) * 4);
-  p.off_cstart = take((size_t)(k + 1) * 4);
-  p.off_rcount = take((size_t)k * 4);
-  p.off_elist = take((size_t)k * 4);
-  p.off_meta = take(16);
-  p.off_order = take((size_t)n * 4);
-  p.off_part = take((size_t)p.nwork * dim * 4);
-  p.off_c0 = take((size_t)k * dim * 4);
-  p.off_c1 = take((size_t)k * dim * 4);
-  p.total = o;
+  size_t vs = kp2d_vpr_scratch_bytes((int)q0, k, dim, 1);
+  if (q1 > 0) vs = std::max(vs, kp2d_vpr_scratch_bytes((int)q1, k, dim, 1));
+  Carve c(scratch);
+  p.cpack = c.take<unsigned char>(kp2d_vpr_packed_bytes(k, dim));
+  p.vpr = c.take<unsigned char>(vs);
+  p.hist = c.take<int>((size_t)p.nslab * k);
+  p.start = c.take<int>((size_t)k + 1);
+  p.cstart = c.take<int>((size_t)k + 1);
+  p.rcount = c.take<int>(k);
+  p.elist = c.take<int>(k);
+  p.meta = c.take<int>(4);
+  p.order = c.take<int>(n);
+  p.part = c.take<float>((size_t)p.nwork * dim);
+  p.c0 = c.take<float>((size_t)k * dim);
+  p.c1 = c.take<float>((size_t)k * dim);
+  p.total = c.bytes();
   return p;
 }
 
@@ -336,22 +339,12 @@ int check_shape(const char* who, int64_t n, int dim, int k) {
 
 // one Lloyd iteration, enqueued on st; arguments are checked by the callers
 int step(const float* x, int64_t n, int dim, const float* cin, int k, uint32_t flags, uint64_t seed, int iteration, float* cout,
-         int64_t* assign, float* dist, int64_t* counts, float* obj, unsigned char* scratch, hipStream_t st) {
-  const KmPlan p = km_plan(n, dim, k);
-  unsigned char* cpack = scratch + p.off_cpack;
-  int* hist = reinterpret_cast<int*>(scratch + p.off_hist);
-  int* start = reinterpret_cast<int*>(scratch + p.off_start);
-  int* cstart = reinterpret_cast<int*>(scratch + p.off_cstart);
-  int* rcount = reinterpret_cast<int*>(scratch + p.off_rcount);
-  int* elist = reinterpret_cast<int*>(scratch + p.off_elist);
-  int* meta = reinterpret_cast<int*>(scratch + p.off_meta);
-  int* order = reinterpret_cast<int*>(scratch + p.off_order);
-  float* part = reinterpret_cast<float*>(scratch + p.off_part);
+         int64_t* assign, float* dist, int64_t* counts, float* obj, const KmPlan& p, hipStream_t st) {
   // a. assign: the flat index's own search, k = 1, the centroids as the database
-  if (int e = launch_vpr_pack(cin, k, dim, cpack, st)) return fail(KP2D_ERR_HIP, "kmeans: pack kernel: %d", e);
+  if (int e = launch_vpr_pack(cin, k, dim, p.cpack, st)) return fail(KP2D_ERR_HIP, "kmeans: pack kernel: %d", e);
   for (int64_t q0 = 0; q0 < n; q0 += QCHUNK) {
     VprSearchArgs a{};
-    a.dbp = cpack;
+    a.dbp = p.cpack;
     a.db = cin;
     a.q = x + q0 * dim;
     a.limit = nullptr;
@@ -360,25 +353,25 @@ int step(const float* x, int64_t n, int dim, const float* cin, int k, uint32_t f
     a.nq = (int)std::min<int64_t>(QCHUNK, n - q0);
     a.k = 1;
     a.fp32 = (flags & KP2D_VPR_FP32) ? 1 : 0;
-    if (int e = launch_vpr_search(a, scratch + p.off_vpr, dist + q0, assign + q0, st)) return fail(KP2D_ERR_HIP, "kmeans: search kernels: %d", e);
+    if (int e = launch_vpr_search(a, p.vpr, dist + q0, assign + q0, st)) return fail(KP2D_ERR_HIP, "kmeans: search kernels: %d", e);
   }
   // b. inverted index by a stable counting sort, then the per-cluster sums
-  HIP_TRY(hipMemsetAsync(hist, 0, (size_t)p.nslab * k * 4, st));
-  hipLaunchKernelGGL(km_hist_kernel, dim3(p.nslab), dim3(256), 0, st, assign, n, p.slab, k, hist);
+  HIP_TRY(hipMemsetAsync(p.hist, 0, (size_t)p.nslab * k * 4, st));
+  hipLaunchKernelGGL(km_hist_kernel, dim3(p.nslab), dim3(256), 0, st, assign, n, p.slab, k, p.hist);
   HIP_TRY(hipGetLastError());
-  hipLaunchKernelGGL(km_colscan_kernel, dim3((k + 255) / 256), dim3(256), 0, st, hist, p.nslab, k, rcount, counts);
+  hipLaunchKernelGGL(km_colscan_kernel, dim3((k + 255) / 256), dim3(256), 0, st, p.hist, p.nslab, k, p.rcount, counts);
   HIP_TRY(hipGetLastError());
-  hipLaunchKernelGGL(km_scan_kernel, dim3(1), dim3(SB), 0, st, rcount, k, start, cstart, elist, meta, dist, assign, n, obj);
+  hipLaunchKernelGGL(km_scan_kernel, dim3(1), dim3(SB), 0, st, p.rcount, k, p.start, p.cstart, p.elist, p.meta, dist, assign, n, obj);
   HIP_TRY(hipGetLastError());
-  hipLaunchKernelGGL(km_scatter_kernel, dim3(p.nslab), dim3(64), 0, st, assign, n, p.slab, k, hist, start, order);
+  hipLaunchKernelGGL(km_scatter_kernel, dim3(p.nslab), dim3(64), 0, st, assign, n, p.slab, k, p.hist, p.start, p.order);
   HIP_TRY(hipGetLastError());
-  hipLaunchKernelGGL(km_sum_kernel, dim3((unsigned)p.nwork), dim3(64), 0, st, x, dim, k, start, cstart, order, part);
+  hipLaunchKernelGGL(km_sum_kernel, dim3((unsigned)p.nwork), dim3(64), 0, st, x, dim, k, p.start, p.cstart, p.order, p.part);
   HIP_TRY(hipGetLastError());
   // c. update
-  hipLaunchKernelGGL(km_update_kernel, dim3(k), dim3(64), 0, st, part, cin, dim, start, cstart, cout);
+  hipLaunchKernelGGL(km_update_kernel, dim3(k), dim3(64), 0, st, p.part, cin, dim, p.start, p.cstart, cout);
   HIP_TRY(hipGetLastError());
   if (!(flags & KP2D_KMEANS_NO_SPLIT)) {
-    hipLaunchKernelGGL(km_split_kernel, dim3(1), dim3(SB), 0, st, cout, dim, k, rcount, elist, meta, seed, iteration);
+    hipLaunchKernelGGL(km_split_kernel, dim3(1), dim3(SB), 0, st, cout, dim, k, p.rcount, p.elist, p.meta, seed, iteration);
     HIP_TRY(hipGetLastError());
   }
   if (flags & KP2D_KMEANS_SPHERICAL) {
@@ -396,7 +389,7 @@ extern "C" {
 
 size_t kp2d_kmeans_scratch_bytes(int64_t n, int dim, int k) {
   if (dim < 16 || dim > 16384 || dim % 16 || k < 1 || k > 65536 || n < k || n > INT32_MAX) return 0;
-  return km_plan(n, dim, k).total;
+  return km_plan(nullptr, n, dim, k).total;
 }
 
 int kp2d_kmeans_step(const float* x, int64_t n, int dim, const float* centroids_in, int k, uint32_t flags, uint64_t seed,
@@ -409,11 +402,10 @@ int kp2d_kmeans_step(const float* x, int64_t n, int dim, const float* centroids_
   if (centroids_in == centroids_out) return fail(KP2D_ERR_ARG, "kmeans_step: centroids_in and centroids_out must differ");
   if ((uintptr_t)x % 16 || (uintptr_t)centroids_in % 16 || (uintptr_t)centroids_out % 16 || (uintptr_t)scratch % 16)
     return fail(KP2D_ERR_ARG, "kmeans_step: x, centroids and scratch must be 16-byte aligned");
-  const size_t need = km_plan(n, dim, k).total;
-  if (scratch_bytes < need) return fail(KP2D_ERR_WORKSPACE, "kmeans scratch %zu B < required %zu B (kp2d_kmeans_scratch_bytes)", scratch_bytes, need);
+  const KmPlan p = km_plan(scratch, n, dim, k);
+  if (scratch_bytes < p.total) return fail(KP2D_ERR_WORKSPACE, "kmeans scratch %zu B < required %zu B (kp2d_kmeans_scratch_bytes)", scratch_bytes, p.total);
   DeviceGuard guard(x, (hipStream_t)stream);
-  return step(x, n, dim, centroids_in, k, flags, seed, iteration, centroids_out, assign, dist, counts, obj,
-              reinterpret_cast<unsigned char*>(scratch), (hipStream_t)stream);
+  return step(x, n, dim, centroids_in, k, flags, seed, iteration, centroids_out, assign, dist, counts, obj, p, (hipStream_t)stream);
 }
 
 int kp2d_kmeans_train(const float* x, int64_t n, int dim, float* centroids, int k, int niter, uint32_t flags, uint64_t seed,
@@ -425,15 +417,14 @@ int kp2d_kmeans_train(const float* x, int64_t n, int dim, float* centroids, int 
   if (!x || !centroids || !assign || !dist || !counts || !obj || !scratch) return fail(KP2D_ERR_ARG, "null argument");
   if ((uintptr_t)x % 16 || (uintptr_t)centroids % 16 || (uintptr_t)scratch % 16)
     return fail(KP2D_ERR_ARG, "kmeans_train: x, centroids and scratch must be 16-byte aligned");
-  const KmPlan p = km_plan(n, dim, k);
+  const KmPlan p = km_plan(scratch, n, dim, k);
   if (scratch_bytes < p.total) return fail(KP2D_ERR_WORKSPACE, "kmeans scratch %zu B < required %zu B (kp2d_kmeans_scratch_bytes)", scratch_bytes, p.total);
   hipStream_t st = (hipStream_t)stream;
   DeviceGuard guard(x, st);
-  unsigned char* sc = reinterpret_cast<unsigned char*>(scratch);
-  float* buf[2] = {reinterpret_cast<float*>(sc + p.off_c0), reinterpret_cast<float*>(sc + p.off_c1)};
+  float* buf[2] = {p.c0, p.c1};
   const float* cur = centroids;                        // iteration i: cur -> buf[i & 1]
   for (int i = 0; i < niter; ++i) {
-    if (int e = step(x, n, dim, cur, k, flags, seed, i, buf[i & 1], assign, dist, counts, obj + i, sc, st)) return e;
+    if (int e = step(x, n, dim, cur, k, flags, seed, i, buf[i & 1], assign, dist, counts, obj + i, p, st)) return e;
     cur = buf[i & 1];
   }
   HIP_TRY(hipMemcpyAsync(centroids, cur, (size_t)k * dim * 4, hipMemcpyDeviceToDevice, st));

@@ -1,6 +1,7 @@
-// The C ABI declared in include/kp2d.h: every entry point checks its arguments and hands over to the model description
-// (model_desc.cpp), the launch plan (plan.cpp) or a kernel launcher.  All arithmetic happens in the HIP kernels of this
-// directory; there is no CPU compute path here (a missing device or library is an error, never a fallback).
+// The model's part of the C ABI declared in include/kp2d.h (create / weights / forward / post / select / options / profiling;
+// the stateless features hold their entry points next to their kernels): every entry point checks its arguments and hands over
+// to the model description (model_desc.cpp), the launch plan (plan.cpp) or a kernel launcher.  All arithmetic happens in the HIP
+// kernels of this directory; there is no CPU compute path here (a missing device or library is an error, never a fallback).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -329,105 +330,6 @@ int kp2d_preprocess(const uint8_t* frames, int B, int Hs, int Ws, float* x, int 
   return KP2D_OK;
 }
 
-// scratch layout of the matcher: [train_best u64 B*max1][rnn_idx i32 B*max1][rnn_dist f32 B*max1][partials]
-static constexpr int kMatchSlices = 16;
-static bool match_wants_slices(int B, int max0, int max1) {
-  // few pairs: the train range of a query is split over several workgroups (match.hip knn2()); needs partial arrays
-  return (long)((std::min(max0, max1) + 63) / 64) * B < 512;
-}
-size_t kp2d_match_scratch_bytes(int B, int max0, int max1) {
-  if (B < 1 || max0 < 1 || max1 < 1) return 0;
-  size_t n = (size_t)B * max1 * 16;
-  if (match_wants_slices(B, max0, max1)) n += (size_t)kMatchSlices * B * std::max(max0, max1) * 12;
-  return (n + 255) & ~(size_t)255;
-}
-
-int kp2d_match_descriptors_ex(const float* d0, const int32_t* n0, const float* d1, const int32_t* n1, int B, int max0,
-                              int max1, int C, float ratio, const int32_t* cls0, const int32_t* cls1, uint32_t flags,
-                              int32_t* nn_idx, float* nn_dist, float* nn_dist2, int32_t* match_q, float* match_d,
-                              void* scratch, size_t scratch_bytes, void* stream) {
-  if (!d0 || !n0 || !d1 || !n1 || !nn_idx || !nn_dist || !nn_dist2 || !match_q || !match_d || !scratch)
-    return fail(KP2D_ERR_ARG, "null argument");
-  if (B < 1 || max0 < 1 || max1 < 1) return fail(KP2D_ERR_ARG, "empty match problem");
-  if ((cls0 == nullptr) != (cls1 == nullptr)) return fail(KP2D_ERR_ARG, "class ids must be given for both sides or neither");
-  if (flags & ~(uint32_t)KP2D_MATCH_MUTUAL) return fail(KP2D_ERR_ARG, "unknown match flags 0x%x", flags);
-  if (scratch_bytes < (size_t)B * max1 * 16) return fail(KP2D_ERR_WORKSPACE, "match scratch %zu B < required %zu B (kp2d_match_scratch_bytes)", scratch_bytes, kp2d_match_scratch_bytes(B, max0, max1));
-  if ((uintptr_t)scratch % 8) return fail(KP2D_ERR_WORKSPACE, "match scratch must be 8-byte aligned");
-  DeviceGuard guard(d0, (hipStream_t)stream);
-  MatchArgs a{d0, d1, n0, n1, B, max0, max1, C, ratio, nn_idx, nn_dist, nn_dist2,
-              reinterpret_cast<unsigned long long*>(scratch), match_q, match_d};
-  a.cls0 = cls0; a.cls1 = cls1;
-  a.mutual = (flags & KP2D_MATCH_MUTUAL) ? 1 : 0;
-  char* p = reinterpret_cast<char*>(scratch) + (size_t)B * max1 * 8;
-  a.rnn_idx = reinterpret_cast<int32_t*>(p); p += (size_t)B * max1 * 4;
-  a.rnn_dist = reinterpret_cast<float*>(p); p += (size_t)B * max1 * 4;
-  const size_t left = scratch_bytes - (size_t)B * max1 * 16;
-  const size_t per_slice = (size_t)B * std::max(max0, max1) * 12;
-  if (match_wants_slices(B, max0, max1) && left >= 2 * per_slice) {
-    a.part_slices = (int)std::min<size_t>(kMatchSlices, left / per_slice);
-    const size_t n = (size_t)a.part_slices * B * std::max(max0, max1);
-    a.part_idx = reinterpret_cast<int32_t*>(p);
-    a.part_d = reinterpret_cast<float*>(p + n * 4);
-    a.part_d2 = reinterpret_cast<float*>(p + n * 8);
-  }
-  int e = launch_match(a, (hipStream_t)stream);
-  if (e) return fail(e < 0 ? KP2D_ERR_UNSUPPORTED : KP2D_ERR_HIP, "match kernels: %d (descriptor width %d)", e, C);
-  return KP2D_OK;
-}
-
-int kp2d_match_descriptors(const float* d0, const int32_t* n0, const float* d1, const int32_t* n1, int B, int max0,
-                           int max1, int C, float ratio, int32_t* nn_idx, float* nn_dist, float* nn_dist2,
-                           int32_t* match_q, float* match_d, void* scratch, void* stream) {
-  if (!d0 || !n0 || !d1 || !n1 || !nn_idx || !nn_dist || !nn_dist2 || !match_q || !match_d || !scratch)
-    return fail(KP2D_ERR_ARG, "null argument");
-  if (B < 1 || max0 < 1 || max1 < 1) return fail(KP2D_ERR_ARG, "empty match problem");
-  DeviceGuard guard(d0, (hipStream_t)stream);
-  MatchArgs a{d0, d1, n0, n1, B, max0, max1, C, ratio, nn_idx, nn_dist, nn_dist2,
-              reinterpret_cast<unsigned long long*>(scratch), match_q, match_d};
-  int e = launch_match(a, (hipStream_t)stream);
-  if (e) return fail(e < 0 ? KP2D_ERR_UNSUPPORTED : KP2D_ERR_HIP, "match kernels: %d (descriptor width %d)", e, C);
-  return KP2D_OK;
-}
-
-int kp2d_match_pairs(const int32_t* match_q, const float* match_d, const float* pts0, const float* pts1, int B, int max0,
-                     int max1, float* pairs, int32_t* idx, float* dist, int32_t* count, void* stream) {
-  if (!match_q || !count || (dist && !match_d) || (pairs && (!pts0 || !pts1))) return fail(KP2D_ERR_ARG, "null argument");
-  if (B < 1 || max0 < 1 || max1 < 1) return fail(KP2D_ERR_ARG, "empty match problem");
-  DeviceGuard guard(match_q, (hipStream_t)stream);
-  PairsArgs a{match_q, match_d, pts0, pts1, B, max0, max1, pairs, idx, dist, count};
-  int e = launch_match_pairs(a, (hipStream_t)stream);
-  if (e) return fail(KP2D_ERR_HIP, "match pairs kernel: %d", e);
-  return KP2D_OK;
-}
-
-int kp2d_match_topk_pairs(int mode, const int32_t* match_q, const int64_t* matches0, const float* val, const float* pts0,
-                          const float* pts1, int B, int max0, int max1, int k, float* pairs, int32_t* idx, float* out_val,
-                          int32_t* count, void* scratch, size_t scratch_bytes, void* stream) {
-  if (mode != KP2D_TOPK_BF && mode != KP2D_TOPK_LG) return fail(KP2D_ERR_ARG, "mode is KP2D_TOPK_BF or KP2D_TOPK_LG");
-  if (!val || !count || !scratch || (mode == KP2D_TOPK_BF ? !match_q : !matches0) || (pairs && (!pts0 || !pts1)))
-    return fail(KP2D_ERR_ARG, "null argument");
-  if (B < 1 || max0 < 1 || max1 < 1) return fail(KP2D_ERR_ARG, "empty match problem");
-  const int n = mode == KP2D_TOPK_BF ? max1 : max0;
-  const int kcap = (k <= 0 || k > n) ? n : k;
-  if (scratch_bytes < kp2d_match_topk_scratch_bytes(B, max0, max1)) return fail(KP2D_ERR_WORKSPACE, "match top-k scratch too small");
-  if (reinterpret_cast<uintptr_t>(scratch) & 3) return fail(KP2D_ERR_ARG, "match top-k scratch must be 4-byte aligned");
-  DeviceGuard guard(val, (hipStream_t)stream);
-  TopkPairsArgs a{};
-  a.mode = mode; a.match_q = match_q; a.matches0 = reinterpret_cast<const long long*>(matches0); a.val = val;
-  a.pts0 = pts0; a.pts1 = pts1; a.B = B; a.n = n; a.max0 = max0; a.max1 = max1; a.kcap = kcap;
-  a.keys = static_cast<float*>(scratch);
-  a.sel = reinterpret_cast<int32_t*>(a.keys + (size_t)B * n);
-  a.pairs = pairs; a.idx = idx; a.out_val = out_val; a.count = count;
-  int e = launch_match_topk_pairs(a, (hipStream_t)stream);
-  if (e) return fail(KP2D_ERR_HIP, "match top-k pairs: %d", e);
-  return KP2D_OK;
-}
-
-size_t kp2d_match_topk_scratch_bytes(int B, int max0, int max1) {
-  const size_t n = (size_t)(max0 > max1 ? max0 : max1);
-  return (size_t)(B > 0 ? B : 0) * n * 8;      // keys [B][n] float + selection [B][<= n] int32
-}
-
 int kp2d_set_profiling(kp2d_model* m, int on) {
   if (!m) return fail(KP2D_ERR_ARG, "null model");
   m->profiling = on != 0;
@@ -508,56 +410,6 @@ int kp2d_set_seg_ids(kp2d_model* m, int64_t* ids, size_t capacity) {
 int kp2d_set_chunk_frames(kp2d_model* m, int frames) {
   if (!m || frames < 0) return fail(KP2D_ERR_ARG, "bad argument");
   m->chunk_frames = frames;
-  return KP2D_OK;
-}
-
-// ---- place recognition (vpr.hip) ----
-static int vpr_dim_check(int dim) {
-  if (dim < 16 || dim > 16384 || dim % 16) return fail(KP2D_ERR_UNSUPPORTED, "vpr: descriptor dim %d (needs dim %% 16 == 0, 16 <= dim <= 16384)", dim);
-  return KP2D_OK;
-}
-size_t kp2d_vpr_packed_bytes(int64_t n, int dim) {
-  if (n < 0 || dim < 16 || dim > 16384 || dim % 16) return 0;
-  return (size_t)n * vpr_row_bytes(dim);
-}
-
-int kp2d_vpr_pack(const float* x, int64_t n, int dim, void* packed, void* stream) {
-  if (int e = vpr_dim_check(dim)) return e;
-  if (n < 0 || n > INT32_MAX) return fail(KP2D_ERR_ARG, "vpr_pack: row count %lld", (long long)n);
-  if (n == 0) return KP2D_OK;
-  if (!x || !packed) return fail(KP2D_ERR_ARG, "null argument");
-  if ((uintptr_t)x % 16 || (uintptr_t)packed % 16) return fail(KP2D_ERR_ARG, "vpr_pack: x and packed must be 16-byte aligned");
-  DeviceGuard guard(x, (hipStream_t)stream);
-  if (int e = launch_vpr_pack(x, n, dim, packed, (hipStream_t)stream)) return fail(KP2D_ERR_HIP, "vpr_pack kernel: %d", e);
-  return KP2D_OK;
-}
-
-size_t kp2d_vpr_scratch_bytes(int nq, int64_t ndb, int dim, int k) {
-  if (nq < 1 || ndb < 0 || ndb > INT32_MAX || dim < 16 || dim > 16384 || dim % 16 || k < 1 || k > 1024) return 0;
-  return vpr_plan(nq, ndb, dim, k).total;
-}
-
-int kp2d_vpr_search(const void* packed_db, const float* db, int64_t ndb, int dim, const float* q, int nq,
-                    const int64_t* limit, int k, uint32_t flags, float* dist, int64_t* idx, void* scratch,
-                    size_t scratch_bytes, void* stream) {
-  if (int e = vpr_dim_check(dim)) return e;
-  if (k < 1 || k > 1024) return fail(KP2D_ERR_ARG, "vpr_search: k = %d outside [1, 1024]", k);
-  if (nq < 0 || ndb < 0) return fail(KP2D_ERR_ARG, "vpr_search: negative size");
-  if (ndb > INT32_MAX) return fail(KP2D_ERR_UNSUPPORTED, "vpr_search: more than 2^31 - 1 database rows");
-  if (flags & ~(uint32_t)KP2D_VPR_FP32) return fail(KP2D_ERR_ARG, "unknown vpr flags 0x%x", flags);
-  if (nq == 0) return KP2D_OK;
-  if (!q || !dist || !idx || !scratch || (ndb > 0 && (!packed_db || !db))) return fail(KP2D_ERR_ARG, "null argument");
-  if ((uintptr_t)q % 16 || (uintptr_t)db % 16 || (uintptr_t)packed_db % 16 || (uintptr_t)scratch % 16)
-    return fail(KP2D_ERR_ARG, "vpr_search: q, db, packed_db and scratch must be 16-byte aligned");
-  const size_t need = kp2d_vpr_scratch_bytes(nq, ndb, dim, k);
-  if (scratch_bytes < need) return fail(KP2D_ERR_WORKSPACE, "vpr scratch %zu B < required %zu B (kp2d_vpr_scratch_bytes)", scratch_bytes, need);
-  DeviceGuard guard(q, (hipStream_t)stream);
-  VprSearchArgs a{};
-  a.dbp = reinterpret_cast<const unsigned char*>(packed_db);
-  a.db = db; a.q = q; a.limit = limit; a.ndb = ndb; a.dim = dim; a.nq = nq; a.k = k;
-  a.fp32 = (flags & KP2D_VPR_FP32) ? 1 : 0;
-  if (int e = launch_vpr_search(a, reinterpret_cast<unsigned char*>(scratch), dist, idx, (hipStream_t)stream))
-    return fail(KP2D_ERR_HIP, "vpr_search kernels: %d", e);
   return KP2D_OK;
 }
 

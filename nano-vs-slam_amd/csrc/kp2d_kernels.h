@@ -1,4 +1,5 @@
-// Internal launch interface between the host code (plan.cpp, kp2d_api.cpp, lightglue_api.cpp) and the HIP kernels.
+// Internal launch interface between the host code (plan.cpp, kp2d_api.cpp, lightglue_api.cpp) and the HIP kernels: only what
+// crosses files (match.hip, keypoint_metrics.hip, dense_metrics.hip keep their argument structs and entry points to themselves).
 // Not part of the public ABI (that is include/kp2d.h).
 #pragma once
 #include <hip/hip_runtime.h>
@@ -178,43 +179,6 @@ struct LgAssignArgs {
 };
 int launch_lg_assign(const LgAssignArgs& a, hipStream_t s);
 
-// ---- descriptor matching (src/visual_odometry/feature_matcher.py:89-98, 179-209) ---------------
-struct MatchArgs {
-  const float* d0; const float* d1;         // [B][max0][C] query / [B][max1][C] train descriptors
-  const int32_t* n0; const int32_t* n1;     // [B] valid rows per pair
-  int B, max0, max1, C;
-  float ratio;
-  int32_t* nn_idx; float* nn_dist; float* nn_dist2;   // [B][max0] k=2 neighbours of every query
-  unsigned long long* train_best;                      // [B][max1] scratch: (distance bits << 32 | query)
-  int32_t* match_q; float* match_d;                    // [B][max1] query matched to each train row (-1: none)
-  // optional (kp2d_match_descriptors_ex):
-  const int32_t* cls0 = nullptr; const int32_t* cls1 = nullptr;   // [B][max0] / [B][max1] class ids: a query sees its own class only
-  int mutual = 0;                                      // 1: mutual nearest neighbours instead of ratio test + one-to-one
-  int32_t* rnn_idx = nullptr; float* rnn_dist = nullptr;          // [B][max1] nearest query of every train row (mutual)
-  int32_t* part_idx = nullptr; float* part_d = nullptr; float* part_d2 = nullptr;   // [slices][B][max(max0,max1)] partial results
-  int part_slices = 0;                                 // train-range slices the partial arrays can hold (few pairs: more workgroups)
-};
-struct PairsArgs {       // compaction of the matched rows of every pair (train order)
-  const int32_t* match_q; const float* match_d;        // [B][max1]
-  const float* pts0; const float* pts1;                // [B][max0][2] / [B][max1][2] keypoints (x, y); may be null with pairs
-  int B, max0, max1;
-  float* pairs;          // [B][max1][4]  x0, y0, x1, y1 of match i (null: skip)
-  int32_t* idx;          // [B][max1][2]  (query row, train row) (null: skip)
-  float* dist;           // [B][max1]     distance (null: skip)
-  int32_t* count;        // [B]
-};
-int launch_match_pairs(const PairsArgs& a, hipStream_t s);
-struct TopkPairsArgs {   // at most kcap matched pairs per frame pair, best first (the VO loop's top_k_matches)
-  int mode;              // 0: BF (match_q [B][n] + match distance, smaller is better; n = max1)   1: LightGlue (matches0 [B][n] int64 + matching score; n = max0)
-  const int32_t* match_q; const long long* matches0; const float* val;
-  const float* pts0; const float* pts1;
-  int B, n, max0, max1, kcap;
-  float* keys; int32_t* sel;       // scratch [B][n] / [B][kcap]
-  float* pairs; int32_t* idx; float* out_val; int32_t* count;
-};
-int launch_match_topk_pairs(const TopkPairsArgs& a, hipStream_t s);
-int launch_match(const MatchArgs& a, hipStream_t s);
-
 // ---- vpr.hip: flat squared-L2 top-k over global descriptors (kp2d_vpr_*) ----------------------
 struct VprSearchArgs {
   const unsigned char* dbp;        // packed database rows (kp2d_vpr_pack: 4 dim + 16 bytes each)
@@ -226,11 +190,9 @@ struct VprSearchArgs {
   int dim, nq, k, fp32;
   unsigned long long* codes;       // per-slice lists (scratch; set by launch_vpr_search)
 };
-struct VprPlan { int nz, G; size_t off_q, off_a, off_b, total; };   // database slices, merge fan-in, scratch layout
-VprPlan vpr_plan(int nq, int64_t ndb, int dim, int k);
-size_t vpr_row_bytes(int dim);
+// (kmeans.hip searches with these two; the scratch is kp2d_vpr_scratch_bytes' for the same arguments)
 int launch_vpr_pack(const float* x, int64_t n, int dim, void* packed, hipStream_t s);
-int launch_vpr_search(VprSearchArgs a, unsigned char* scratch, float* dist, int64_t* idx, hipStream_t s);
+int launch_vpr_search(VprSearchArgs a, void* scratch, float* dist, int64_t* idx, hipStream_t s);
 
 // ---- small layout / elementwise kernels -----------------------------------------------------
 int launch_preprocess(const unsigned char* src, float* dst, int B, int Hs, int Ws, int H, int W, hipStream_t s);

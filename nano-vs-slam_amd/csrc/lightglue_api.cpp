@@ -181,21 +181,25 @@ int pack(kp2d_lg* m, std::vector<float>& blob) {
   return KP2D_OK;
 }
 
+// workspace of a forward, every piece on an ALIGN boundary
 struct Ws {
-  size_t x, t3, ctx, msg, hb, cs, fz, rp_m, rp_s, cp_m, cp_s, rmax, rarg, cmax, carg, cnt, total;
+  float *x, *t3, *ctx, *msg, *hb, *cs, *fz;
+  float *rp_m, *rp_s, *cp_m, *cp_s, *rmax, *cmax;     // per-tile partials of the assignment (LgAssignArgs)
+  int *rarg, *carg;
+  int32_t* cnt;                                       // [n0 | n1]: key counts of the 2B sequences (kp2d_lg_forward_counts)
+  size_t total;
 };
-Ws layout(const kp2d_lg* m, int B, int M, int N) {
+Ws layout(void* workspace, const kp2d_lg* m, int B, int M, int N) {
   const size_t R = (size_t)B * (M + N), d = m->cfg.descriptor_dim, hd = d / m->cfg.num_heads;
+  Carve c(workspace);
   Ws w{};
-  size_t off = 0;
-  auto take = [&](size_t floats) { size_t o = off; off = align_up(off + floats * 4); return o; };
-  w.x = take(R * d); w.t3 = take(R * 3 * d); w.ctx = take(R * d); w.msg = take(R * d); w.hb = take(R * 2 * d);
-  w.cs = take(R * hd); w.fz = take(R * (d + 32));
+  w.x = c.take<float>(R * d); w.t3 = c.take<float>(R * 3 * d); w.ctx = c.take<float>(R * d); w.msg = c.take<float>(R * d);
+  w.hb = c.take<float>(R * 2 * d); w.cs = c.take<float>(R * hd); w.fz = c.take<float>(R * (d + 32));
   const size_t rp = (size_t)B * ((N + 63) / 64) * M, cp = (size_t)B * ((M + 63) / 64) * N;      // per-tile partials
-  w.rp_m = take(rp); w.rp_s = take(rp); w.cp_m = take(cp); w.cp_s = take(cp);
-  w.rmax = take(rp); w.rarg = take(rp); w.cmax = take(cp); w.carg = take(cp);
-  w.cnt = take((size_t)2 * B);      // [n0 | n1]: key counts of the 2B sequences (kp2d_lg_forward_counts)
-  w.total = off;
+  w.rp_m = c.take<float>(rp); w.rp_s = c.take<float>(rp); w.cp_m = c.take<float>(cp); w.cp_s = c.take<float>(cp);
+  w.rmax = c.take<float>(rp); w.rarg = c.take<int>(rp); w.cmax = c.take<float>(cp); w.carg = c.take<int>(cp);
+  w.cnt = c.take<int32_t>((size_t)2 * B);
+  w.total = c.bytes();
   return w;
 }
 
@@ -267,7 +271,7 @@ int kp2d_lg_finalize_weights(kp2d_lg* m) {
 
 size_t kp2d_lg_workspace_bytes(const kp2d_lg* m, int B, int M, int N) {
   if (!m || B < 1 || M < 1 || N < 1) return 0;
-  return layout(m, B, M, N).total;
+  return layout(nullptr, m, B, M, N).total;
 }
 
 int kp2d_lg_forward(kp2d_lg* m, const float* kpts0, const float* kpts1, const float* desc0, const float* desc1,
@@ -292,17 +296,15 @@ int kp2d_lg_forward_counts(kp2d_lg* m, const float* kpts0, const float* kpts1, c
   if (B < 1 || M < 1 || N < 1) return fail(KP2D_ERR_ARG, "B, M, N must be >= 1");
   if ((long)B * (M + N) > (1l << 24)) return fail(KP2D_ERR_ARG, "too many keypoints in one call");
   if ((uintptr_t)workspace % ALIGN) return fail(KP2D_ERR_WORKSPACE, "workspace must be %zu-byte aligned", ALIGN);
-  const Ws w = layout(m, B, M, N);
+  const Ws w = layout(workspace, m, B, M, N);
   if (workspace_bytes < w.total) return fail(KP2D_ERR_WORKSPACE, "workspace %zu B < required %zu B", workspace_bytes, w.total);
   kp2d::DeviceGuard guard(m->cfg.device);
   hipStream_t st = (hipStream_t)stream;
-  char* base = (char*)workspace;
-  auto F = [&](size_t off) { return reinterpret_cast<float*>(base + off); };
   const int d = m->cfg.descriptor_dim, din = m->cfg.input_dim, heads = m->cfg.num_heads, hd = d / heads;
   const int R = B * (M + N), R0 = B * M;
-  float *X = F(w.x), *T3 = F(w.t3), *CTX = F(w.ctx), *MSG = F(w.msg), *HB = F(w.hb), *CS = F(w.cs), *FZ = F(w.fz);
+  float *X = w.x, *T3 = w.t3, *CTX = w.ctx, *MSG = w.msg, *HB = w.hb, *CS = w.cs, *FZ = w.fz;
   // padded keypoint sets: [n0 | n1] as the key counts of the 2B sequences the attention launches walk
-  int32_t* CNT = n0 ? reinterpret_cast<int32_t*>(base + w.cnt) : nullptr;
+  int32_t* CNT = n0 ? w.cnt : nullptr;
   if (n0) {
     HIP_TRY(hipMemcpyAsync(CNT, n0, (size_t)B * 4, hipMemcpyDeviceToDevice, st));
     HIP_TRY(hipMemcpyAsync(CNT + B, n1, (size_t)B * 4, hipMemcpyDeviceToDevice, st));
@@ -446,9 +448,8 @@ int kp2d_lg_forward_counts(kp2d_lg* m, const float* kpts0, const float* kpts1, c
     if (!fused || m->cfg.n_layers == 0) LG_CHECK(launch_lg_linear(a, st), "log_assignment.final_proj");
     LgAssignArgs g{};
     g.fz = FZ; g.fs = d + 32; g.D = d; g.B = B; g.M = M; g.N = N; g.scores = log_assignment;
-    g.rp_m = F(w.rp_m); g.rp_s = F(w.rp_s); g.cp_m = F(w.cp_m); g.cp_s = F(w.cp_s);
-    g.rmax = F(w.rmax); g.cmax = F(w.cmax);
-    g.rarg = reinterpret_cast<int*>(base + w.rarg); g.carg = reinterpret_cast<int*>(base + w.carg);
+    g.rp_m = w.rp_m; g.rp_s = w.rp_s; g.cp_m = w.cp_m; g.cp_s = w.cp_s;
+    g.rmax = w.rmax; g.cmax = w.cmax; g.rarg = w.rarg; g.carg = w.carg;
     g.th = filter_threshold;
     g.cnt0 = n0; g.cnt1 = n1;
     g.matches0 = matches0; g.matches1 = matches1; g.mscores0 = mscores0; g.mscores1 = mscores1;

@@ -15,10 +15,49 @@
 //   pairs_kernel    compacts the matched rows of a pair into (x0, y0, x1, y1) / (q, t) / distance lists (train order)
 // Batched over B frame pairs with per-pair descriptor counts, so the per-frame D2H copy + CPU matcher of the
 // reference disappears.  HBM-light (descriptors are tiny); bound by VALU: n0*n1*C*3 ops per pair.
+// The entry points (kp2d_match_*, include/kp2d.h) are at the end of the file, behind the two scratch layouts.
+#include <algorithm>
+#include <cstdint>
+
+#include "api_common.h"
+#include "device_guard.h"
 #include "kp2d_kernels.h"
 #include "options.h"
 
 namespace kp2d {
+
+struct MatchArgs {
+  const float* d0; const float* d1;         // [B][max0][C] query / [B][max1][C] train descriptors
+  const int32_t* n0; const int32_t* n1;     // [B] valid rows per pair
+  int B, max0, max1, C;
+  float ratio;
+  int32_t* nn_idx; float* nn_dist; float* nn_dist2;   // [B][max0] k=2 neighbours of every query
+  unsigned long long* train_best;                      // [B][max1] scratch: (distance bits << 32 | query)
+  int32_t* match_q; float* match_d;                    // [B][max1] query matched to each train row (-1: none)
+  // optional (kp2d_match_descriptors_ex):
+  const int32_t* cls0 = nullptr; const int32_t* cls1 = nullptr;   // [B][max0] / [B][max1] class ids: a query sees its own class only
+  int mutual = 0;                                      // 1: mutual nearest neighbours instead of ratio test + one-to-one
+  int32_t* rnn_idx = nullptr; float* rnn_dist = nullptr;          // [B][max1] nearest query of every train row (mutual)
+  int32_t* part_idx = nullptr; float* part_d = nullptr; float* part_d2 = nullptr;   // [slices][B][max(max0,max1)] partial results
+  int part_slices = 0;                                 // train-range slices the partial arrays can hold (few pairs: more workgroups)
+};
+struct PairsArgs {       // compaction of the matched rows of every pair (train order)
+  const int32_t* match_q; const float* match_d;        // [B][max1]
+  const float* pts0; const float* pts1;                // [B][max0][2] / [B][max1][2] keypoints (x, y); may be null with pairs
+  int B, max0, max1;
+  float* pairs;          // [B][max1][4]  x0, y0, x1, y1 of match i (null: skip)
+  int32_t* idx;          // [B][max1][2]  (query row, train row) (null: skip)
+  float* dist;           // [B][max1]     distance (null: skip)
+  int32_t* count;        // [B]
+};
+struct TopkPairsArgs {   // at most kcap matched pairs per frame pair, best first (the VO loop's top_k_matches)
+  int mode;              // 0: BF (match_q [B][n] + match distance, smaller is better; n = max1)   1: LightGlue (matches0 [B][n] int64 + matching score; n = max0)
+  const int32_t* match_q; const long long* matches0; const float* val;
+  const float* pts0; const float* pts1;
+  int B, n, max0, max1, kcap;
+  float* keys; int32_t* sel;       // scratch [B][n] / [B][kcap]
+  float* pairs; int32_t* idx; float* out_val; int32_t* count;
+};
 
 constexpr int MQ = 64;    // queries per workgroup (4 threads each)
 // train descriptors per LDS tile; rows are padded by 4 floats: the four rows a wave reads together (one per `part`) then
@@ -465,7 +504,7 @@ static int knn2(const MatchArgs& a, bool reverse, int32_t* idx, float* dist, flo
   return 0;
 }
 
-int launch_match(const MatchArgs& a, hipStream_t s) {
+static int launch_match(const MatchArgs& a, hipStream_t s) {
   if (a.C != 32 && a.C != 64 && a.C != 128) return -1500;
   if ((a.cls0 == nullptr) != (a.cls1 == nullptr)) return -1501;
   bool assigned = false;
@@ -518,7 +557,7 @@ __global__ __launch_bounds__(256) void match_topk_gather_kernel(const TopkPairsA
     reinterpret_cast<float4*>(a.pairs)[oo] = pr;
   }
 }
-int launch_match_topk_pairs(const TopkPairsArgs& a, hipStream_t s) {
+static int launch_match_topk_pairs(const TopkPairsArgs& a, hipStream_t s) {
   hipLaunchKernelGGL(match_topk_keys_kernel, dim3((a.n + 255) / 256, a.B), dim3(256), 0, s, a);
   TopkArgs t{a.keys, a.B, a.n, a.kcap, -INFINITY, a.sel, nullptr, a.count};
   if (int e = launch_topk(t, s)) return e;
@@ -526,9 +565,133 @@ int launch_match_topk_pairs(const TopkPairsArgs& a, hipStream_t s) {
   return (int)hipGetLastError();
 }
 
-int launch_match_pairs(const PairsArgs& a, hipStream_t s) {
+static int launch_match_pairs(const PairsArgs& a, hipStream_t s) {
   hipLaunchKernelGGL(match_pairs_kernel, dim3(a.B), dim3(256), 0, s, a);
   return (int)hipGetLastError();
 }
 
+// ---- scratch layouts: one walk each (api_common.h Carve) fills the argument struct's scratch pointers and gives the size ----
+constexpr int kMatchSlices = 16;
+static bool match_wants_slices(int B, int max0, int max1) {
+  // few pairs: the train range of a query is split over several workgroups (knn2()); needs partial arrays
+  return (long)((std::min(max0, max1) + 63) / 64) * B < 512;
+}
+
+// [train_best u64 | rnn_idx i32 | rnn_dist f32] of B * max1 rows each, then [part_idx i32 | part_d f32 | part_d2 f32] of
+// slices * B * max(max0, max1) rows each; pieces packed at their natural alignment, the total rounded to ALIGN.
+// avail: the bytes the caller has (SIZE_MAX: the size query).  Partials are laid out for min(kMatchSlices, what fits behind
+// the base arrays) slices; a scratch that holds fewer than two runs without slices (the documented degradation).
+struct MatchBytes { size_t base, all; };      // the base arrays alone (the least a call needs) / everything laid out
+static MatchBytes match_layout(void* scratch, size_t avail, MatchArgs& a) {
+  Carve c(scratch);
+  const size_t n1 = (size_t)a.B * a.max1, nm = (size_t)a.B * std::max(a.max0, a.max1);
+  a.train_best = c.take<unsigned long long>(n1, 8);
+  a.rnn_idx = c.take<int32_t>(n1, 4);
+  a.rnn_dist = c.take<float>(n1, 4);
+  const size_t base = c.end, fit = avail < base ? 0 : (avail - base) / (nm * 12);
+  if (match_wants_slices(a.B, a.max0, a.max1) && fit >= 2) {
+    a.part_slices = (int)std::min<size_t>(kMatchSlices, fit);
+    a.part_idx = c.take<int32_t>(a.part_slices * nm, 4);
+    a.part_d = c.take<float>(a.part_slices * nm, 4);
+    a.part_d2 = c.take<float>(a.part_slices * nm, 4);
+  }
+  return {base, c.bytes()};
+}
+
+// keys [B][n] float, selection [B][<= n] int32.  The size query lays out n = max(max0, max1); a call lays out its mode's n.
+static size_t topk_layout(void* scratch, TopkPairsArgs& a) {
+  Carve c(scratch);
+  const size_t bn = (size_t)(a.B > 0 ? a.B : 0) * (size_t)a.n;
+  a.keys = c.take<float>(bn, 4);
+  a.sel = c.take<int32_t>(bn, 4);
+  return c.end;
+}
+
 }  // namespace kp2d
+
+using namespace kp2d;
+
+extern "C" {
+
+size_t kp2d_match_scratch_bytes(int B, int max0, int max1) {
+  if (B < 1 || max0 < 1 || max1 < 1) return 0;
+  MatchArgs a{};
+  a.B = B; a.max0 = max0; a.max1 = max1;
+  return match_layout(nullptr, SIZE_MAX, a).all;
+}
+
+int kp2d_match_descriptors_ex(const float* d0, const int32_t* n0, const float* d1, const int32_t* n1, int B, int max0,
+                              int max1, int C, float ratio, const int32_t* cls0, const int32_t* cls1, uint32_t flags,
+                              int32_t* nn_idx, float* nn_dist, float* nn_dist2, int32_t* match_q, float* match_d,
+                              void* scratch, size_t scratch_bytes, void* stream) {
+  if (!d0 || !n0 || !d1 || !n1 || !nn_idx || !nn_dist || !nn_dist2 || !match_q || !match_d || !scratch)
+    return fail(KP2D_ERR_ARG, "null argument");
+  if (B < 1 || max0 < 1 || max1 < 1) return fail(KP2D_ERR_ARG, "empty match problem");
+  if ((cls0 == nullptr) != (cls1 == nullptr)) return fail(KP2D_ERR_ARG, "class ids must be given for both sides or neither");
+  if (flags & ~(uint32_t)KP2D_MATCH_MUTUAL) return fail(KP2D_ERR_ARG, "unknown match flags 0x%x", flags);
+  MatchArgs a{d0, d1, n0, n1, B, max0, max1, C, ratio, nn_idx, nn_dist, nn_dist2, nullptr, match_q, match_d};
+  a.cls0 = cls0; a.cls1 = cls1;
+  a.mutual = (flags & KP2D_MATCH_MUTUAL) ? 1 : 0;
+  if (scratch_bytes < match_layout(scratch, scratch_bytes, a).base) return fail(KP2D_ERR_WORKSPACE, "match scratch %zu B < required %zu B (kp2d_match_scratch_bytes)", scratch_bytes, kp2d_match_scratch_bytes(B, max0, max1));
+  if ((uintptr_t)scratch % 8) return fail(KP2D_ERR_WORKSPACE, "match scratch must be 8-byte aligned");
+  DeviceGuard guard(d0, (hipStream_t)stream);
+  int e = launch_match(a, (hipStream_t)stream);
+  if (e) return fail(e < 0 ? KP2D_ERR_UNSUPPORTED : KP2D_ERR_HIP, "match kernels: %d (descriptor width %d)", e, C);
+  return KP2D_OK;
+}
+
+int kp2d_match_descriptors(const float* d0, const int32_t* n0, const float* d1, const int32_t* n1, int B, int max0,
+                           int max1, int C, float ratio, int32_t* nn_idx, float* nn_dist, float* nn_dist2,
+                           int32_t* match_q, float* match_d, void* scratch, void* stream) {
+  if (!d0 || !n0 || !d1 || !n1 || !nn_idx || !nn_dist || !nn_dist2 || !match_q || !match_d || !scratch)
+    return fail(KP2D_ERR_ARG, "null argument");
+  if (B < 1 || max0 < 1 || max1 < 1) return fail(KP2D_ERR_ARG, "empty match problem");
+  DeviceGuard guard(d0, (hipStream_t)stream);
+  // the first form's scratch is the one-to-one table alone (B * max1 * 8 bytes): no layout to walk
+  MatchArgs a{d0, d1, n0, n1, B, max0, max1, C, ratio, nn_idx, nn_dist, nn_dist2,
+              static_cast<unsigned long long*>(scratch), match_q, match_d};
+  int e = launch_match(a, (hipStream_t)stream);
+  if (e) return fail(e < 0 ? KP2D_ERR_UNSUPPORTED : KP2D_ERR_HIP, "match kernels: %d (descriptor width %d)", e, C);
+  return KP2D_OK;
+}
+
+int kp2d_match_pairs(const int32_t* match_q, const float* match_d, const float* pts0, const float* pts1, int B, int max0,
+                     int max1, float* pairs, int32_t* idx, float* dist, int32_t* count, void* stream) {
+  if (!match_q || !count || (dist && !match_d) || (pairs && (!pts0 || !pts1))) return fail(KP2D_ERR_ARG, "null argument");
+  if (B < 1 || max0 < 1 || max1 < 1) return fail(KP2D_ERR_ARG, "empty match problem");
+  DeviceGuard guard(match_q, (hipStream_t)stream);
+  PairsArgs a{match_q, match_d, pts0, pts1, B, max0, max1, pairs, idx, dist, count};
+  int e = launch_match_pairs(a, (hipStream_t)stream);
+  if (e) return fail(KP2D_ERR_HIP, "match pairs kernel: %d", e);
+  return KP2D_OK;
+}
+
+size_t kp2d_match_topk_scratch_bytes(int B, int max0, int max1) {
+  TopkPairsArgs a{};
+  a.B = B; a.n = max0 > max1 ? max0 : max1;
+  return topk_layout(nullptr, a);
+}
+
+int kp2d_match_topk_pairs(int mode, const int32_t* match_q, const int64_t* matches0, const float* val, const float* pts0,
+                          const float* pts1, int B, int max0, int max1, int k, float* pairs, int32_t* idx, float* out_val,
+                          int32_t* count, void* scratch, size_t scratch_bytes, void* stream) {
+  if (mode != KP2D_TOPK_BF && mode != KP2D_TOPK_LG) return fail(KP2D_ERR_ARG, "mode is KP2D_TOPK_BF or KP2D_TOPK_LG");
+  if (!val || !count || !scratch || (mode == KP2D_TOPK_BF ? !match_q : !matches0) || (pairs && (!pts0 || !pts1)))
+    return fail(KP2D_ERR_ARG, "null argument");
+  if (B < 1 || max0 < 1 || max1 < 1) return fail(KP2D_ERR_ARG, "empty match problem");
+  const int n = mode == KP2D_TOPK_BF ? max1 : max0;
+  const int kcap = (k <= 0 || k > n) ? n : k;
+  if (scratch_bytes < kp2d_match_topk_scratch_bytes(B, max0, max1)) return fail(KP2D_ERR_WORKSPACE, "match top-k scratch too small");
+  if (reinterpret_cast<uintptr_t>(scratch) & 3) return fail(KP2D_ERR_ARG, "match top-k scratch must be 4-byte aligned");
+  DeviceGuard guard(val, (hipStream_t)stream);
+  TopkPairsArgs a{};
+  a.mode = mode; a.match_q = match_q; a.matches0 = reinterpret_cast<const long long*>(matches0); a.val = val;
+  a.pts0 = pts0; a.pts1 = pts1; a.B = B; a.n = n; a.max0 = max0; a.max1 = max1; a.kcap = kcap;
+  topk_layout(scratch, a);
+  a.pairs = pairs; a.idx = idx; a.out_val = out_val; a.count = count;
+  int e = launch_match_topk_pairs(a, (hipStream_t)stream);
+  if (e) return fail(KP2D_ERR_HIP, "match top-k pairs: %d", e);
+  return KP2D_OK;
+}
+
+}  // extern "C"

@@ -20,10 +20,14 @@
 // Determinism: a key depends on its query, its row and its tile's mode only (tiles are fixed 128-row blocks of the
 // database and slices are whole tiles), every reduction runs in a fixed order, and lists are cut by the total order of
 // (key, row).  A query's answer is therefore bit-identical for any batch of queries and any number of slices.
+// The entry points (kp2d_vpr_*, include/kp2d.h) are at the end of the file; kmeans.hip uses the two launchers directly.
 #include <algorithm>
 #include <cfloat>
+#include <cstdint>
 #include <utility>
 
+#include "api_common.h"
+#include "device_guard.h"
 #include "kp2d_kernels.h"
 
 namespace kp2d {
@@ -337,9 +341,9 @@ __global__ __launch_bounds__(256) void vpr_final_kernel(const unsigned long long
   }
 }
 
-}  // namespace
-
-VprPlan vpr_plan(int nq, int64_t ndb, int dim, int k) {
+// database slices and merge fan-in of a search
+struct VprPlan { int nz, G; };
+VprPlan vpr_plan(int nq, int64_t ndb, int k) {
   VprPlan p{};
   const int64_t T = (ndb + RB - 1) / RB;
   const int qb = (nq + QB - 1) / QB;
@@ -349,26 +353,36 @@ VprPlan vpr_plan(int nq, int64_t ndb, int dim, int k) {
   const int64_t per = T > 0 ? (T + nz - 1) / nz : 1;
   p.nz = T > 0 ? (int)((T + per - 1) / per) : 1;
   p.G = std::max(2, MERGE_CAND / k);
-  const size_t list = (size_t)nq * k * 8;
-  p.off_q = 0;
-  p.off_a = ((size_t)nq * row_bytes(dim) + 255) & ~(size_t)255;
-  p.off_b = p.off_a + ((p.nz * list + 255) & ~(size_t)255);
-  const int n1 = p.nz > 1 ? (p.nz + p.G - 1) / p.G : 0;
-  p.total = p.off_b + n1 * list;
   return p;
 }
 
-size_t vpr_row_bytes(int dim) { return row_bytes(dim); }
+// scratch: the packed queries (a.qp), the nz slices' lists (a.codes), and the lists of the first merge level (the levels
+// alternate between the two); every piece on an ALIGN boundary, the total not rounded
+struct VprScratch { unsigned long long* merged; size_t bytes; };
+VprScratch vpr_layout(void* scratch, const VprPlan& p, VprSearchArgs& a) {
+  Carve c(scratch);
+  const size_t list = (size_t)a.nq * a.k;
+  a.qp = c.take<unsigned char>((size_t)a.nq * row_bytes(a.dim));
+  a.codes = c.take<unsigned long long>(p.nz * list);
+  unsigned long long* merged = c.take<unsigned long long>((p.nz > 1 ? (p.nz + p.G - 1) / p.G : 0) * list);
+  return {merged, c.end};
+}
+
+int vpr_dim_check(int dim) {
+  if (dim < 16 || dim > 16384 || dim % 16) return fail(KP2D_ERR_UNSUPPORTED, "vpr: descriptor dim %d (needs dim %% 16 == 0, 16 <= dim <= 16384)", dim);
+  return KP2D_OK;
+}
+
+}  // namespace
 
 int launch_vpr_pack(const float* x, int64_t n, int dim, void* packed, hipStream_t s) {
   if (n > 0) hipLaunchKernelGGL(vpr_pack_kernel, dim3((unsigned)n), dim3(256), 0, s, x, dim, (unsigned char*)packed);
   return (int)hipGetLastError();
 }
 
-int launch_vpr_search(VprSearchArgs a, unsigned char* scratch, float* dist, int64_t* idx, hipStream_t s) {
-  const VprPlan p = vpr_plan(a.nq, a.ndb, a.dim, a.k);
-  a.qp = scratch + p.off_q;
-  a.codes = reinterpret_cast<unsigned long long*>(scratch + p.off_a);
+int launch_vpr_search(VprSearchArgs a, void* scratch, float* dist, int64_t* idx, hipStream_t s) {
+  const VprPlan p = vpr_plan(a.nq, a.ndb, a.k);
+  unsigned long long* other = vpr_layout(scratch, p, a).merged;
   if (a.ndb == 0) {
     hipLaunchKernelGGL(vpr_final_kernel, dim3(a.nq), dim3(256), 0, s, nullptr, a.db, a.q, a.dim, a.k, dist, idx);
     return (int)hipGetLastError();
@@ -376,7 +390,6 @@ int launch_vpr_search(VprSearchArgs a, unsigned char* scratch, float* dist, int6
   if (!a.fp32) hipLaunchKernelGGL(vpr_pack_kernel, dim3(a.nq), dim3(256), 0, s, a.q, a.dim, const_cast<unsigned char*>(a.qp));
   hipLaunchKernelGGL(vpr_search_kernel, dim3((a.nq + QB - 1) / QB, p.nz), dim3(256), 0, s, a);
   unsigned long long* cur = a.codes;
-  unsigned long long* other = reinterpret_cast<unsigned long long*>(scratch + p.off_b);
   int nz = p.nz;
   while (nz > 1) {
     const int nout = (nz + p.G - 1) / p.G;
@@ -389,3 +402,55 @@ int launch_vpr_search(VprSearchArgs a, unsigned char* scratch, float* dist, int6
 }
 
 }  // namespace kp2d
+
+using namespace kp2d;
+
+extern "C" {
+
+size_t kp2d_vpr_packed_bytes(int64_t n, int dim) {
+  if (n < 0 || dim < 16 || dim > 16384 || dim % 16) return 0;
+  return (size_t)n * row_bytes(dim);
+}
+
+int kp2d_vpr_pack(const float* x, int64_t n, int dim, void* packed, void* stream) {
+  if (int e = vpr_dim_check(dim)) return e;
+  if (n < 0 || n > INT32_MAX) return fail(KP2D_ERR_ARG, "vpr_pack: row count %lld", (long long)n);
+  if (n == 0) return KP2D_OK;
+  if (!x || !packed) return fail(KP2D_ERR_ARG, "null argument");
+  if ((uintptr_t)x % 16 || (uintptr_t)packed % 16) return fail(KP2D_ERR_ARG, "vpr_pack: x and packed must be 16-byte aligned");
+  DeviceGuard guard(x, (hipStream_t)stream);
+  if (int e = launch_vpr_pack(x, n, dim, packed, (hipStream_t)stream)) return fail(KP2D_ERR_HIP, "vpr_pack kernel: %d", e);
+  return KP2D_OK;
+}
+
+size_t kp2d_vpr_scratch_bytes(int nq, int64_t ndb, int dim, int k) {
+  if (nq < 1 || ndb < 0 || ndb > INT32_MAX || dim < 16 || dim > 16384 || dim % 16 || k < 1 || k > 1024) return 0;
+  VprSearchArgs a{};
+  a.nq = nq; a.dim = dim; a.k = k;
+  return vpr_layout(nullptr, vpr_plan(nq, ndb, k), a).bytes;
+}
+
+int kp2d_vpr_search(const void* packed_db, const float* db, int64_t ndb, int dim, const float* q, int nq,
+                    const int64_t* limit, int k, uint32_t flags, float* dist, int64_t* idx, void* scratch,
+                    size_t scratch_bytes, void* stream) {
+  if (int e = vpr_dim_check(dim)) return e;
+  if (k < 1 || k > 1024) return fail(KP2D_ERR_ARG, "vpr_search: k = %d outside [1, 1024]", k);
+  if (nq < 0 || ndb < 0) return fail(KP2D_ERR_ARG, "vpr_search: negative size");
+  if (ndb > INT32_MAX) return fail(KP2D_ERR_UNSUPPORTED, "vpr_search: more than 2^31 - 1 database rows");
+  if (flags & ~(uint32_t)KP2D_VPR_FP32) return fail(KP2D_ERR_ARG, "unknown vpr flags 0x%x", flags);
+  if (nq == 0) return KP2D_OK;
+  if (!q || !dist || !idx || !scratch || (ndb > 0 && (!packed_db || !db))) return fail(KP2D_ERR_ARG, "null argument");
+  if ((uintptr_t)q % 16 || (uintptr_t)db % 16 || (uintptr_t)packed_db % 16 || (uintptr_t)scratch % 16)
+    return fail(KP2D_ERR_ARG, "vpr_search: q, db, packed_db and scratch must be 16-byte aligned");
+  const size_t need = kp2d_vpr_scratch_bytes(nq, ndb, dim, k);
+  if (scratch_bytes < need) return fail(KP2D_ERR_WORKSPACE, "vpr scratch %zu B < required %zu B (kp2d_vpr_scratch_bytes)", scratch_bytes, need);
+  DeviceGuard guard(q, (hipStream_t)stream);
+  VprSearchArgs a{};
+  a.dbp = static_cast<const unsigned char*>(packed_db);
+  a.db = db; a.q = q; a.limit = limit; a.ndb = ndb; a.dim = dim; a.nq = nq; a.k = k;
+  a.fp32 = (flags & KP2D_VPR_FP32) ? 1 : 0;
+  if (int e = launch_vpr_search(a, scratch, dist, idx, (hipStream_t)stream)) return fail(KP2D_ERR_HIP, "vpr_search kernels: %d", e);
+  return KP2D_OK;
+}
+
+}  // extern "C"

@@ -15,12 +15,10 @@ definitions (include/kp2d.h states the rule).  There is no CPU path behind the k
 """
 from __future__ import annotations
 
-import ctypes as C
-
 import torch
 
-from . import _lib
-from .vpr import _ptr
+from . import _dev, _lib
+from ._dev import ptr as _ptr, stream as _stream
 
 SEG_MAX_CLASSES = 1024
 SEG_CONF_MAX_CLASSES = 256
@@ -39,17 +37,12 @@ def seg_conf_lds_max() -> int:
     return int(_lib.load().kp2d_seg_conf_lds_max())
 
 
-def _stream(dev):
-    return C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-
-
 def _maps(output, target):
     """[B, H, W] / [B, 1, H, W] integer class maps -> (pred [B, n] int64, target [B, n] uint8 / int32 / int64), contiguous."""
     for name, t in (("output", output), ("target", target)):
         if not isinstance(t, torch.Tensor):
             raise TypeError(f"{name} must be a torch tensor")
-        if t.device.type != "cuda":
-            raise RuntimeError(f"{name}: CPU tensors are not supported (no CPU fallback); pass device tensors")
+        _dev.require_device(name, t)
         if t.dtype not in _INT_DTYPES:
             raise TypeError(f"{name} must hold integer class ids, got {t.dtype}")
         if t.dim() < 2:
@@ -150,16 +143,6 @@ def f1_score(tp, fp, fn, tn, reduction=None, zero_division=1.0):
     return _reduce(lambda tp, fp, fn, tn: (2 * tp, 2 * tp + fn + fp), tp, fp, fn, tn, reduction, zero_division)
 
 
-def _model_device(model):
-    dev = getattr(model, "device", None)
-    if dev is None:
-        dev = next(model.parameters()).device
-    dev = torch.device(dev)
-    if dev.type == "cuda" and dev.index is None:
-        dev = torch.device("cuda", torch.cuda.current_device())
-    return dev
-
-
 def evaluate_segmentation(model, dataloader, n_classes, debug=False):
     """Drop-in for the reference's evaluate_segmentation (src/evaluation/segmentation.py:8-91): every sample
     {"image", "seg"} goes through the model and its post_processing, the class map is scored against ``seg`` with
@@ -169,7 +152,7 @@ def evaluate_segmentation(model, dataloader, n_classes, debug=False):
     that, which overstates every score and divides by zero on a single batch.  ``debug`` windows are not reproduced."""
     model.eval()
     model.training = False
-    dev = _model_device(model)
+    dev = _dev.model_device(model)
     total, batches = None, 0
     with torch.no_grad():
         for sample in dataloader:
@@ -193,8 +176,7 @@ def _depth_maps(gt, pred, valid):
     for name, t in (("gt", gt), ("pred", pred)) + ((("valid", valid),) if valid is not None else ()):
         if not isinstance(t, torch.Tensor):
             raise TypeError(f"{name} must be a torch tensor")
-        if t.device.type != "cuda":
-            raise RuntimeError(f"{name}: CPU tensors are not supported (no CPU fallback); pass device tensors")
+        _dev.require_device(name, t)
         if t.dim() < 2 or t.shape[0] != gt.shape[0] or t.device != gt.device:
             raise ValueError(f"{name} must be [B, ...] on gt's device with gt's batch size, got {tuple(t.shape)}")
     B = gt.shape[0]
@@ -221,11 +203,11 @@ def depth_sums(gt, pred, valid=None, min_depth=None, max_depth=None):
     dev = g.device
     lib = _lib.load()
     sums = torch.empty(B, DEPTH_NSUMS, dtype=torch.float64, device=dev)
-    scratch = torch.empty(max(int(lib.kp2d_depth_scratch_bytes(B, n)), 256), dtype=torch.uint8, device=dev)
+    ws = _dev.scratch(lib.kp2d_depth_scratch_bytes(B, n), dev)
     lo = float("nan") if min_depth is None else float(min_depth)
     hi = float("nan") if max_depth is None else float(max_depth)
     with torch.cuda.device(dev):
-        _lib.check(lib.kp2d_depth_sums(_ptr(g), _ptr(p), _ptr(v), B, n, lo, hi, _ptr(sums), _ptr(scratch), scratch.numel(),
+        _lib.check(lib.kp2d_depth_sums(_ptr(g), _ptr(p), _ptr(v), B, n, lo, hi, _ptr(sums), _ptr(ws), ws.numel(),
                                        _stream(dev)))
     return sums
 
@@ -264,7 +246,7 @@ def evaluate_depth_estimation(model, dataloader, debug=False):
     windows are not reproduced."""
     model.eval()
     model.training = False
-    dev = _model_device(model)
+    dev = _dev.model_device(model)
     total, batches = None, 0
     with torch.no_grad():
         for sample in dataloader:

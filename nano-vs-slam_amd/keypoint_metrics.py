@@ -20,28 +20,20 @@ their places.  There is no CPU path behind the kernels: CPU tensors raise.
 """
 from __future__ import annotations
 
-import ctypes as C
-
 import numpy as np
 import torch
 
-from . import _lib
-from .vpr import _ptr
+from . import _dev, _lib
+from ._dev import ptr as _ptr, stream as _stream
 
 DESC_WIDTHS = (32, 64, 128)
 CONF_THRESHOLD = 0.7                          # keypoints.py:84
 
 
-def _stream(dev):
-    return C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-
-
 def _dev_tensor(name, t):
     if not isinstance(t, torch.Tensor):
         raise TypeError(f"{name} must be a torch tensor")
-    if t.device.type != "cuda":
-        raise RuntimeError(f"{name}: CPU tensors are not supported (no CPU fallback); pass device tensors")
-    return t.detach()
+    return _dev.require_device(name, t).detach()
 
 
 def _sets(pts0, cnt0, pts1, cnt1, hom):
@@ -62,10 +54,6 @@ def _sets(pts0, cnt0, pts1, cnt1, hom):
             hom.reshape(B, 9).to(torch.float64).contiguous())
 
 
-def _scratch(lib, B, k0, k1, Cd, keep_k, dev):
-    return torch.empty(max(int(lib.kp2d_kp_scratch_bytes(B, k0, k1, Cd, keep_k)), 256), dtype=torch.uint8, device=dev)
-
-
 def repeatability_stats(pts0, cnt0, pts1, cnt1, hom, image_shape, keep_k=300, distance_thresh=3):
     """kp2d_kp_repeatability on device tensors: pts0 [B,k0,3] / pts1 [B,k1,3] rows (x, y, prob), cnt0 / cnt1 [B] rows that
     exist, hom [B,3,3] (image 0 -> image 1), image_shape = (b0, b1) as the reference passes it ((H, W); x is held against
@@ -77,7 +65,7 @@ def repeatability_stats(pts0, cnt0, pts1, cnt1, hom, image_shape, keep_k=300, di
     lib = _lib.load()
     counts = torch.empty(B, 4, dtype=torch.int64, device=dev)
     le = torch.empty(B, 2, dtype=torch.float64, device=dev)
-    scratch = _scratch(lib, B, k0, k1, 0, int(keep_k), dev)
+    scratch = _dev.scratch(lib.kp2d_kp_scratch_bytes(B, k0, k1, 0, int(keep_k)), dev)
     with torch.cuda.device(dev):
         _lib.check(lib.kp2d_kp_repeatability(_ptr(pts0), _ptr(cnt0), _ptr(pts1), _ptr(cnt1), _ptr(hom), B, k0, k1,
                                              float(image_shape[0]), float(image_shape[1]), int(keep_k), float(distance_thresh),
@@ -100,7 +88,7 @@ def matching_score_stats(pts0, cnt0, desc0, pts1, cnt1, desc1, hom, image_shape,
     desc0, desc1 = desc0.to(torch.float32).contiguous(), desc1.to(torch.float32).contiguous()
     lib = _lib.load()
     counts = torch.empty(B, 4, dtype=torch.int64, device=dev)
-    scratch = _scratch(lib, B, k0, k1, Cd if Cd in DESC_WIDTHS else 0, int(keep_k), dev)
+    scratch = _dev.scratch(lib.kp2d_kp_scratch_bytes(B, k0, k1, Cd if Cd in DESC_WIDTHS else 0, int(keep_k)), dev)
     with torch.cuda.device(dev):
         _lib.check(lib.kp2d_kp_matching_score(_ptr(pts0), _ptr(cnt0), _ptr(desc0), _ptr(pts1), _ptr(cnt1), _ptr(desc1), _ptr(hom),
                                               B, k0, k1, Cd, float(image_shape[0]), float(image_shape[1]), int(keep_k),
@@ -212,8 +200,7 @@ def evaluate_keypoint_net(data_loader, keypoint_net, output_shape=(320, 240), to
     One host read at the end."""
     keypoint_net.eval()
     keypoint_net.training = False
-    from .dense_metrics import _model_device
-    dev = _model_device(keypoint_net)
+    dev = _dev.model_device(keypoint_net)
     shape = tuple(output_shape[::-1])
     reps, locs, mss = [], [], []
     with torch.no_grad():

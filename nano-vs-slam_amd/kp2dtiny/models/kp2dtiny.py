@@ -27,7 +27,8 @@ import os
 import torch
 from torch import nn
 
-from ... import _lib
+from ... import _dev, _lib
+from ..._dev import ptr as _ptr, stream as _stream
 
 # ---------------------------------------------------------------------------------------------
 # configuration tables (reference: models/kp2dtiny.py:46-218).  Values are the reference's data.
@@ -270,8 +271,8 @@ class _NetVLAD(_Holder):
         for a unit c, so the two largest dots of a descriptor belong to its two nearest unit centres and their
         difference is half the gap of the two squared distances, which the flat index's top-2 gives directly."""
         if isinstance(clsts, torch.Tensor) and isinstance(traindescs, torch.Tensor):
-            if clsts.device.type != "cuda" or traindescs.device.type != "cuda":
-                raise RuntimeError("init_params: CPU tensors are not supported (no CPU fallback); pass numpy or device tensors")
+            for t in (clsts, traindescs):
+                _dev.require_device("init_params", t, "pass numpy or device tensors")
             import math
             from ...vpr import FlatL2Index
             clsts = clsts.detach().to(torch.float32).contiguous()
@@ -399,10 +400,6 @@ class _Engine:
             self._ws_call = prev
 
 
-def _ptr(t):
-    return C.c_void_p(t.data_ptr()) if t is not None else C.c_void_p()
-
-
 class _KP2DTinyBase(nn.Module):
     """Shared host logic of KP2DTinyV2 / KP2DTinyV3."""
 
@@ -500,8 +497,7 @@ class _KP2DTinyBase(nn.Module):
         eng = self._get_engine(torch.device(device))
         n = eng.lib.kp2d_packed_bytes(eng.handle)
         buf = torch.empty(n, dtype=torch.uint8, device=device)
-        s = torch.cuda.current_stream(buf.device)
-        _lib.check(eng.lib.kp2d_export_packed(eng.handle, _ptr(buf), C.c_void_p(s.cuda_stream)))
+        _lib.check(eng.lib.kp2d_export_packed(eng.handle, _ptr(buf), _stream(buf.device)))
         return buf
 
     def load_packed_weights(self, buf: torch.Tensor):
@@ -516,8 +512,7 @@ class _KP2DTinyBase(nn.Module):
             self.__dict__["_engine"] = eng
         if buf.numel() != eng.lib.kp2d_packed_bytes(eng.handle):
             raise ValueError("packed weight blob has the wrong size for this configuration")
-        s = torch.cuda.current_stream(dev)
-        _lib.check(eng.lib.kp2d_import_packed(eng.handle, _ptr(buf), C.c_void_p(s.cuda_stream)))
+        _lib.check(eng.lib.kp2d_import_packed(eng.handle, _ptr(buf), _stream(dev)))
         eng.signature = self._weights_signature()
         self._apply_precision(eng)
 
@@ -565,7 +560,7 @@ class _KP2DTinyBase(nn.Module):
         depth = torch.empty(B, 1, H2, W2, device=dev) if self.depth else None
         ws = eng.workspace(B, H, W, dev)
         flags = 0 if self.training else _lib.KP2D_FWD_EVAL
-        stream = torch.cuda.current_stream(dev).cuda_stream
+        stream = _stream(dev)
         # inference mode: the layer that writes `seg` also writes the dense class map post_processing starts with (its
         # tile of logits is in LDS anyway), so post_processing need not read the logits again — if it gets THIS tensor,
         # unmodified (see post_processing)
@@ -587,11 +582,11 @@ class _KP2DTinyBase(nn.Module):
     def _run_forward(self, eng, x, frames, B, H, W, flags, score, shift, feat, seg, vlad, depth, ws, stream):
         if frames is None:
             _lib.check(eng.lib.kp2d_forward(eng.handle, _ptr(x), B, H, W, flags, _ptr(score), _ptr(shift), _ptr(feat),
-                                            _ptr(seg), _ptr(vlad), _ptr(depth), _ptr(ws), ws.numel(), C.c_void_p(stream)))
+                                            _ptr(seg), _ptr(vlad), _ptr(depth), _ptr(ws), ws.numel(), stream))
         else:
             _lib.check(eng.lib.kp2d_forward_frames(eng.handle, _ptr(frames), B, frames.shape[1], frames.shape[2], H, W, flags,
                                                    _ptr(score), _ptr(shift), _ptr(feat), _ptr(seg), _ptr(vlad), _ptr(depth),
-                                                   _ptr(ws), ws.numel(), C.c_void_p(stream)))
+                                                   _ptr(ws), ws.numel(), stream))
 
     def post_processing(self, out, H, W):
         """Reference: post_processing kp2dtiny.py:593-625 / :959-993 (mutates and returns ``out``)."""
@@ -621,10 +616,9 @@ class _KP2DTinyBase(nn.Module):
             else:
                 seg_ids = (torch.empty(B, 1, Hc, Wc, dtype=torch.int64, device=dev) if self.sample_segmentation
                            else torch.empty(B, 1, Hs, Ws, dtype=torch.int64, device=dev))
-        stream = torch.cuda.current_stream(dev).cuda_stream
         _lib.check(eng.lib.kp2d_post(eng.handle, _ptr(score), _ptr(shift), _ptr(feat), _ptr(seg), B, int(H), int(W),
                                      Hc, Wc, fc, Hf, Wf, sc, Hs, Ws, _ptr(score_out), _ptr(coord), _ptr(desc),
-                                     _ptr(seg_ids), int(bool(self.sample_segmentation)), C.c_void_p(stream)))
+                                     _ptr(seg_ids), int(bool(self.sample_segmentation)), _stream(dev)))
         if sample:
             out["seg"] = seg_ids
             feat = desc
@@ -697,10 +691,8 @@ class _KP2DTinyBase(nn.Module):
             raise ValueError(f"H and W must be divisible by {q} (got {H}x{W})")
         enc = torch.empty(B, self.encoder_dim, H // self.cell, W // self.cell, device=x.device)
         ws = eng.workspace(B, H, W, x.device)
-        stream = torch.cuda.current_stream(x.device).cuda_stream
-        null = C.c_void_p()
-        _lib.check(eng.lib.kp2d_forward(eng.handle, _ptr(x), B, H, W, _lib.KP2D_FWD_ONLY_ENCODER, null, null, null, null,
-                                        _ptr(enc), null, _ptr(ws), ws.numel(), C.c_void_p(stream)))
+        _lib.check(eng.lib.kp2d_forward(eng.handle, _ptr(x), B, H, W, _lib.KP2D_FWD_ONLY_ENCODER, None, None, None, None,
+                                        _ptr(enc), None, _ptr(ws), ws.numel(), _stream(x.device)))
         return enc
 
 

@@ -15,6 +15,7 @@ import torch
 from torch import nn
 
 from .. import _lib
+from .._dev import ptr as _ptr, stream as _stream
 
 
 class _Holder(nn.Module):
@@ -76,10 +77,6 @@ class _Conf(dict):
 
     def __setattr__(self, k, v):
         self[k] = v
-
-
-def _ptr(t):
-    return C.c_void_p(t.data_ptr()) if t is not None else C.c_void_p()
 
 
 class LightGlue(nn.Module):
@@ -239,11 +236,10 @@ class LightGlue(nn.Module):
             if self._ws is None or self._ws.numel() < need or self._ws.device != dev:
                 self._ws = torch.empty(need, dtype=torch.uint8, device=dev)
             ws = self._ws
-        stream = torch.cuda.current_stream(dev).cuda_stream
         _lib.check(lib.kp2d_lg_forward_counts(h, _ptr(kpts0), _ptr(kpts1), _ptr(desc0), _ptr(desc1), _ptr(size0), _ptr(size1),
                                               _ptr(cnt0), _ptr(cnt1), b, m, n, float(self.conf.filter_threshold), _ptr(scores),
                                               _ptr(m0), _ptr(m1), _ptr(ms0), _ptr(ms1), _ptr(ref0), _ptr(ref1),
-                                              _ptr(ws), ws.numel(), C.c_void_p(stream)))
+                                              _ptr(ws), ws.numel(), _stream(dev)))
         # (no pruning is built: every point survives all layers; one fill instead of two ones_like * n)
         prune = torch.full((b * (m + n),), float(self.conf.n_layers), device=dev)
         return {

@@ -14,17 +14,12 @@ matched by HIP kernels (kp2d_match_descriptors_ex) straight from the [B,k,C] ten
 """
 from __future__ import annotations
 
-import ctypes as C
-
 import torch
 
 from . import _lib
+from ._dev import ptr as _ptr, stream as _stream
 
 MATCH_MUTUAL = 1
-
-
-def _ptr(t):
-    return C.c_void_p(t.data_ptr()) if t is not None else None
 
 
 def match_descriptors(desc0: torch.Tensor, cnt0: torch.Tensor, desc1: torch.Tensor, cnt1: torch.Tensor,
@@ -56,12 +51,11 @@ def match_descriptors(desc0: torch.Tensor, cnt0: torch.Tensor, desc1: torch.Tens
                "match_d": torch.empty(B, k1, device=dev),
                "_scratch": torch.empty((nbytes + 7) // 8, dtype=torch.int64, device=dev)}
     scratch = out["_scratch"]
-    stream = torch.cuda.current_stream(dev).cuda_stream
     _lib.check(lib.kp2d_match_descriptors_ex(_ptr(desc0), _ptr(cnt0), _ptr(desc1), _ptr(cnt1), B, k0, k1, Cd, float(ratio),
                                              _ptr(cls0), _ptr(cls1), MATCH_MUTUAL if mutual else 0,
                                              _ptr(out["nn_idx"]), _ptr(out["nn_dist"]), _ptr(out["nn_dist2"]),
                                              _ptr(out["match_q"]), _ptr(out["match_d"]), _ptr(scratch),
-                                             scratch.numel() * 8, C.c_void_p(stream)))
+                                             scratch.numel() * 8, _stream(dev)))
     return out
 
 
@@ -80,9 +74,8 @@ def match_pairs(match: dict, pts0: torch.Tensor | None = None, pts1: torch.Tenso
             out["pairs"] = torch.empty(B, k1, 4, device=dev)
     if pts0 is not None:
         pts0, pts1 = pts0.contiguous().float(), pts1.contiguous().float()
-    stream = torch.cuda.current_stream(dev).cuda_stream
     _lib.check(lib.kp2d_match_pairs(_ptr(mq), _ptr(md), _ptr(pts0), _ptr(pts1), B, k0, k1, _ptr(out.get("pairs")), _ptr(out["idx"]),
-                                    _ptr(out["dist"]), _ptr(out["count"]), C.c_void_p(stream)))
+                                    _ptr(out["dist"]), _ptr(out["count"]), _stream(dev)))
     return out
 
 
@@ -127,10 +120,9 @@ def match_topk_pairs(k: int, pts0: torch.Tensor | None, pts1: torch.Tensor | Non
             out["pairs"] = torch.empty(B, kcap, 4, device=dev)
     if pts0 is not None:
         pts0, pts1 = pts0.contiguous().float(), pts1.contiguous().float()
-    stream = torch.cuda.current_stream(dev).cuda_stream
     _lib.check(lib.kp2d_match_topk_pairs(mode, _ptr(src_i), _ptr(src_l), _ptr(val), _ptr(pts0), _ptr(pts1), B, max0, max1, int(k),
                                          _ptr(out.get("pairs")), _ptr(out["idx"]), _ptr(out["val"]), _ptr(out["count"]),
-                                         _ptr(out["_scratch"]), out["_scratch"].numel() * 8, C.c_void_p(stream)))
+                                         _ptr(out["_scratch"]), out["_scratch"].numel() * 8, _stream(dev)))
     return out
 
 

@@ -11,13 +11,13 @@ Differences, all on purpose:
 """
 from __future__ import annotations
 
-import ctypes as C
 import os
 
 import numpy as np
 import torch
 
-from . import _lib
+from . import _dev, _lib
+from ._dev import ptr as _ptr, stream as _stream
 from .selectors import select_keypoints, select_keypoints_host
 
 
@@ -67,9 +67,7 @@ def frames_to_input(frames, device, size=None) -> torch.Tensor:
     B, Hs, Ws, _ = t.shape
     H, W = (Hs, Ws) if size is None else (int(size[0]), int(size[1]))
     x = torch.empty(B, 3, H, W, device=dev)
-    stream = torch.cuda.current_stream(dev).cuda_stream
-    _lib.check(_lib.load().kp2d_preprocess(C.c_void_p(t.data_ptr()), B, Hs, Ws, C.c_void_p(x.data_ptr()), H, W,
-                                           C.c_void_p(stream)))
+    _lib.check(_lib.load().kp2d_preprocess(_ptr(t), B, Hs, Ws, _ptr(x), H, W, _stream(dev)))
     return x
 
 
@@ -223,7 +221,7 @@ class FrameStream:
         eng = self.net._get_engine(self.dev)
         if self._slot_ws[slot] is None:
             need = eng.lib.kp2d_workspace_bytes(eng.handle, 1, self.H, self.W)
-            self._slot_ws[slot] = torch.empty(max(int(need), 256), dtype=torch.uint8, device=self.dev)
+            self._slot_ws[slot] = _dev.scratch(need, self.dev)
         with eng.using_workspace(self._slot_ws[slot]):
             if _fused_front(self.net) and not self.zero_copy:
                 # frame in device memory: the first layer reads it (kp2d_forward_frames)
@@ -232,10 +230,8 @@ class FrameStream:
                 # zero-copy slot (pinned host memory): ONE pass over PCIe by the preprocess kernel; the fused first layer
                 # would fetch every halo / bilinear tap across the bus again
                 x = torch.empty(1, 3, self.H, self.W, device=self.dev)
-                stream = torch.cuda.current_stream(self.dev).cuda_stream
                 Hs, Ws = self.dev_in[slot].shape[1:3]
-                _lib.check(lib.kp2d_preprocess(C.c_void_p(self.dev_in[slot].data_ptr()), 1, Hs, Ws, C.c_void_p(x.data_ptr()),
-                                               self.H, self.W, C.c_void_p(stream)))
+                _lib.check(lib.kp2d_preprocess(_ptr(self.dev_in[slot]), 1, Hs, Ws, _ptr(x), self.H, self.W, _stream(self.dev)))
                 fwd = self.net(x)
         out = self.net.post_processing(fwd, self.H, self.W)
         from .selectors import _cap, select_and_gather
@@ -263,7 +259,7 @@ class FrameStream:
             k = rp["pts"].shape[1]
             need = self.lg.workspace_bytes(1, k, k, self.dev)
             if self._lg_ws[cur] is None or self._lg_ws[cur].numel() < need:
-                self._lg_ws[cur] = torch.empty(max(need, 256), dtype=torch.uint8, device=self.dev)
+                self._lg_ws[cur] = _dev.scratch(need, self.dev)
             with self.lg.using_workspace(self._lg_ws[cur]):
                 mo = self.lg(data)
             po = match_topk_pairs(self.top_k_matches, rp["pts"], rc["pts"], matches0=mo["matches0"],
@@ -510,7 +506,7 @@ class BatchStream:
         B, _, H, W = x.shape
         need = int(self._eng.lib.kp2d_workspace_bytes(self._eng.handle, B, H, W))
         if self._ws[slot] is None or self._ws[slot].numel() < need:
-            self._ws[slot] = torch.empty(max(need, 256), dtype=torch.uint8, device=self.dev)
+            self._ws[slot] = _dev.scratch(need, self.dev)
         with torch.cuda.stream(st), torch.no_grad(), self._eng.using_workspace(self._ws[slot]):
             x.record_stream(st)
             out = self.net.post_processing(self.net(x), H, W)
@@ -551,14 +547,13 @@ class BatchStream:
         self._held[slot] = t if zero_copy else None
         need = int(self._eng.lib.kp2d_workspace_bytes(self._eng.handle, B, H, W))
         if self._ws[slot] is None or self._ws[slot].numel() < need:
-            self._ws[slot] = torch.empty(max(need, 256), dtype=torch.uint8, device=self.dev)
+            self._ws[slot] = _dev.scratch(need, self.dev)
         with torch.cuda.stream(st), torch.no_grad(), self._eng.using_workspace(self._ws[slot]):
             if zero_copy or not _fused_front(self.net):
                 if not zero_copy:
                     t = t.to(self.dev, non_blocking=True)
                 x = torch.empty(B, 3, H, W, device=self.dev)
-                _lib.check(_lib.load().kp2d_preprocess(C.c_void_p(t.data_ptr()), B, Hs, Ws, C.c_void_p(x.data_ptr()), H, W,
-                                                       C.c_void_p(st.cuda_stream)))
+                _lib.check(_lib.load().kp2d_preprocess(_ptr(t), B, Hs, Ws, _ptr(x), H, W, _stream(self.dev)))
                 fwd = self.net(x)
             else:
                 # pageable frames: torch's staged upload on this slot's stream, then straight into the first layer

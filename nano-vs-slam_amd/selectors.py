@@ -12,15 +12,10 @@ torch.topk's order; K1/K2 callers only depend on the selected SET.
 """
 from __future__ import annotations
 
-import ctypes as C
-
 import torch
 
 from . import _lib
-
-
-def _ptr(t):
-    return C.c_void_p(t.data_ptr()) if t is not None else C.c_void_p()
+from ._dev import ptr as _ptr, stream as _stream
 
 
 def select_topk(score: torch.Tensor, k: int, thr: float = float("-inf")):
@@ -37,8 +32,7 @@ def select_topk(score: torch.Tensor, k: int, thr: float = float("-inf")):
     idx = torch.empty(B, k, dtype=torch.int32, device=s.device)
     val = torch.empty(B, k, dtype=torch.float32, device=s.device)
     cnt = torch.empty(B, dtype=torch.int32, device=s.device)
-    stream = torch.cuda.current_stream(s.device).cuda_stream
-    _lib.check(lib.kp2d_select_topk(_ptr(s), B, n, k, float(thr), _ptr(idx), _ptr(val), _ptr(cnt), C.c_void_p(stream)))
+    _lib.check(lib.kp2d_select_topk(_ptr(s), B, n, k, float(thr), _ptr(idx), _ptr(val), _ptr(cnt), _stream(s.device)))
     return idx, val, cnt
 
 
@@ -51,9 +45,8 @@ def gather_keypoints(coord: torch.Tensor, desc: torch.Tensor, idx: torch.Tensor)
     coord, desc, idx = coord.contiguous(), desc.contiguous(), idx.contiguous()
     pts = torch.empty(B, k, 2, device=desc.device)
     dsel = torch.empty(B, k, Cd, device=desc.device)
-    stream = torch.cuda.current_stream(desc.device).cuda_stream
     _lib.check(lib.kp2d_gather_keypoints(_ptr(coord), _ptr(desc), _ptr(idx), B, Cd, n, k, _ptr(pts), _ptr(dsel),
-                                         C.c_void_p(stream)))
+                                         _stream(desc.device)))
     return pts, dsel
 
 
@@ -78,9 +71,8 @@ def select_and_gather(score: torch.Tensor, coord: torch.Tensor, desc: torch.Tens
     cnt = torch.empty(B, dtype=torch.int32, device=s.device)
     pts = torch.empty(B, k, 2, device=s.device)
     dsel = torch.empty(B, k, Cd, device=s.device)
-    stream = torch.cuda.current_stream(s.device).cuda_stream
     _lib.check(lib.kp2d_select_keypoints(_ptr(s), _ptr(coord), _ptr(desc), B, Cd, n, k, float(thr), _ptr(idx), _ptr(val),
-                                         _ptr(cnt), _ptr(pts), _ptr(dsel), C.c_void_p(stream)))
+                                         _ptr(cnt), _ptr(pts), _ptr(dsel), _stream(s.device)))
     return idx, val, cnt, pts, dsel
 
 

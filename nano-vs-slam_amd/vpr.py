@@ -12,12 +12,11 @@ There is no CPU path: CPU tensors raise, like the rest of the product.
 """
 from __future__ import annotations
 
-import ctypes as C
-
 import numpy as np
 import torch
 
-from . import _lib
+from . import _dev, _lib
+from ._dev import ptr as _ptr, stream as _stream
 
 VPR_FP32 = 1
 PRECISIONS = {"f16x3": 0, "fp32": VPR_FP32}
@@ -34,10 +33,6 @@ def check_dim(d: int) -> int:
 def row_bytes(d: int) -> int:
     """Bytes of one packed database row (|x|^2, scale and guard bit, then the split-fp16 hi and lo planes)."""
     return 4 * d + 16
-
-
-def _ptr(t):
-    return C.c_void_p(t.data_ptr()) if t is not None else None
 
 
 class FlatL2Index:
@@ -69,8 +64,7 @@ class FlatL2Index:
                 raise ValueError(f"{what} must be [n, {self.d}], got {tuple(t.shape)}")
             t = t.to(self.device)
         elif isinstance(x, torch.Tensor):
-            if x.device.type != "cuda":
-                raise RuntimeError(f"{what}: CPU tensors are not supported (no CPU fallback); pass numpy or a device tensor")
+            _dev.require_device(what, x, "pass numpy or a device tensor")
             if x.dim() != 2 or x.shape[1] != self.d:
                 raise ValueError(f"{what} must be [n, {self.d}], got {tuple(x.shape)}")
             t, is_np = x.to(self.device, torch.float32).contiguous(), False
@@ -95,9 +89,8 @@ class FlatL2Index:
                 npk[:self.ntotal * row_bytes(self.d)] = self._p[:self.ntotal * row_bytes(self.d)]
             self._x, self._p = nx, npk
         self._x[self.ntotal:need] = x
-        stream = torch.cuda.current_stream(self.device).cuda_stream
         dst = self._p[self.ntotal * row_bytes(self.d):]
-        _lib.check(lib.kp2d_vpr_pack(_ptr(self._x[self.ntotal:need]), n, self.d, _ptr(dst), C.c_void_p(stream)))
+        _lib.check(lib.kp2d_vpr_pack(_ptr(self._x[self.ntotal:need]), n, self.d, _ptr(dst), _stream(self.device)))
         self.ntotal = need
 
     def search(self, x, k: int, limit=None):
@@ -111,8 +104,8 @@ class FlatL2Index:
         lim = None
         if limit is not None:
             lim = torch.as_tensor(np.asarray(limit) if not isinstance(limit, torch.Tensor) else limit)
-            if lim.device.type == "cpu" and isinstance(limit, torch.Tensor):
-                raise RuntimeError("search: CPU tensors are not supported (no CPU fallback)")
+            if isinstance(limit, torch.Tensor):
+                _dev.require_device("search", lim, None)
             lim = lim.to(self.device, torch.int64).contiguous().reshape(-1)
             if lim.numel() != nq:
                 raise ValueError(f"limit must have one entry per query ({nq}), got {lim.numel()}")
@@ -122,11 +115,10 @@ class FlatL2Index:
             lib = _lib.load()
             nbytes = int(lib.kp2d_vpr_scratch_bytes(nq, self.ntotal, self.d, k))
             if self._scratch is None or self._scratch.numel() < nbytes:
-                self._scratch = torch.empty(max(nbytes, 256), dtype=torch.uint8, device=self.device)
-            stream = torch.cuda.current_stream(self.device).cuda_stream
+                self._scratch = _dev.scratch(nbytes, self.device)
             _lib.check(lib.kp2d_vpr_search(_ptr(self._p) if self.ntotal else None, _ptr(self._x) if self.ntotal else None,
                                            self.ntotal, self.d, _ptr(q), nq, _ptr(lim), k, PRECISIONS[self.precision],
-                                           _ptr(D), _ptr(I), _ptr(self._scratch), self._scratch.numel(), C.c_void_p(stream)))
+                                           _ptr(D), _ptr(I), _ptr(self._scratch), self._scratch.numel(), _stream(self.device)))
         if is_np:
             return D.cpu().numpy(), I.cpu().numpy()
         return D, I
