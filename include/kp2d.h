@@ -303,6 +303,88 @@ size_t kp2d_vpr_scratch_bytes(int nq, int64_t ndb, int dim, int k);
 int kp2d_vpr_search(const void* packed_db, const float* db, int64_t ndb, int dim, const float* q, int nq,
                     const int64_t* limit, int k, uint32_t flags, float* dist, int64_t* idx, void* scratch,
                     size_t scratch_bytes, void* stream);
+/* kp2d_vpr_search_masked: kp2d_vpr_search restricted to a per-query subset of the database rows.
+ *   Mask format (one format for every call that takes or writes a mask): uint32 words, [nq, W] with
+ *     W = ceil(ndb / 32); row r of query i is bit r & 31 of word i W + (r >> 5).  Bits at or past ndb are zero on
+ *     output and ignored on input.  mask: 4-byte aligned, required (non-NULL) when ndb > 0.
+ *   Everything else is kp2d_vpr_search's: the same packed database, the same scratch (kp2d_vpr_scratch_bytes), the same
+ *     key arithmetic in both precisions, the same range guard, the same (key, row) total order, merge, fp32 re-score and
+ *     (FLT_MAX, -1) padding where a query's mask holds fewer than k rows (an empty mask: every slot is padding).  The
+ *     accuracy text above holds with "the database" read as "the rows of the query's mask".
+ *   A 128-row block of the database whose mask words are zero for all 64 queries of a workgroup is skipped before its
+ *     products: a search over a few positives touches a few blocks.
+ *   Determinism: as above.  A key depends on its query, its row and its block's mode only, and a skipped block holds no
+ *     row of any of the workgroup's queries, so a query's result is bit-identical whatever nq is, whichever other queries
+ *     share the call and whatever their masks are. */
+int kp2d_vpr_search_masked(const void* packed_db, const float* db, int64_t ndb, int dim, const float* q, int nq,
+                           const uint32_t* mask, int k, uint32_t flags, float* dist, int64_t* idx, void* scratch,
+                           size_t scratch_bytes, void* stream);
+
+/* ---- Triplet mining: geographic radius masks, lists, one mining round (nano-vs-slam_amd/csrc/mining.hip) ----------
+ * Replaces the two sklearn.neighbors.NearestNeighbors jobs of the reference's dataset classes (src/data/pittsburgh.py,
+ * the same code in src/data/tokyo247.py): ground truth from UTM positions by radius_neighbors (getPositives :189-200,
+ * the non-trivial positives and potential negatives of QueryDatasetFromStruct.__init__ :258-289) and the hard-triplet
+ * mining of QueryDatasetFromStruct.__getitem__ (:295-333).  Stateless like the calls above: caller-owned device buffers,
+ * the caller's stream; masks in the format stated at kp2d_vpr_search_masked.  nq >= 0, 0 <= ndb < 2^31.
+ *
+ * kp2d_geo_radius_mask: db_xy [ndb,2], q_xy [nq,2] FLOAT64 (8-byte aligned), radius >= 0 (not NaN) ->
+ *   mask [nq, W] uint32, count [nq] int32 (set bits per query).  Row r is inside for query i when
+ *     dx * dx + dy * dy <= radius * radius,   dx = db_x[r] - q_x[i],  dy = db_y[r] - q_y[i],
+ *   every operation a separately rounded float64 operation (NO fused multiply-add): the CLOSED ball, which is what
+ *   sklearn's radius_neighbors returns.  float64 on purpose: UTM northings near 4.5e6 m are 0.5 m apart in fp32.
+ *   flags & KP2D_GEO_INVERT: the complement among rows [0, ndb) (the reference's potential negatives).  Every word of
+ *   mask is written by exactly one wave (ballot-packed), no atomics; no synchronisation.
+ *
+ * kp2d_mask_lists: mask [nq, W] and lims [nq + 1] int64 on the device, lims[0] = 0, lims[i + 1] - lims[i] = the number
+ *   of rows of query i (the caller's cumulative sum of count) -> idx [idx_len] int64 with idx_len = lims[nq]: query i's
+ *   rows in ASCENDING order at idx[lims[i] .. lims[i + 1]) (scipy's / faiss's range-search layout; the reference sorts
+ *   its lists, :271-273).  status: one int32 on the device, the call's own.  Nothing is written outside a query's span
+ *   or outside [0, idx_len).  When a query's popcount disagrees with its span the call returns KP2D_ERR_ARG; to say so
+ *   it waits for the stream (the caller has read lims[nq] from the device to size idx anyway).
+ *
+ * kp2d_vpr_mine: one mining round for nq queries, enqueued on the stream with no host round trip.
+ *   In: the packed database and its fp32 rows (as kp2d_vpr_search), q [nq,dim]; qid [nq] int32 or NULL: the number each
+ *     query is drawn under (NULL: its position i in the call), so a subset of queries draws what the whole set draws;
+ *     pos_mask (the non-trivial positives) and
+ *     neg_mask (the potential negatives), [nq, W]; neg_cache [nq, n_neg] int32 padded with -1 (last round's neg_idx), or
+ *     NULL; n_sample >= 0 draws; 1 <= n_neg, 1 <= n_neg_factor, n_neg * n_neg_factor within [1, 1024]; margin >= 0;
+ *     seed, round >= 0; flags: KP2D_VPR_FP32.  dim as the index's (else KP2D_ERR_UNSUPPORTED); q, db, packed_db and
+ *     scratch 16-byte aligned, the masks and int32 / float arrays 4-byte, pos_idx 8-byte; violations: KP2D_ERR_ARG.
+ *   a. Candidates: cand(i) = { cache rows in [0, ndb) } U { the n_sample draws }.  With nPot(i) the number of set bits of
+ *      neg_mask[i], draw j is u = mix(mix(mix(seed + 0x9E3779B97F4A7C15) ^ (round << 32 | qid[i])) ^ j) mod nPot(i) (mix:
+ *      the splitmix64 finaliser kp2d_kmeans_step's split uses; 64-bit unsigned arithmetic, round and qid as uint32) and selects
+ *      the row of rank u among the set bits, ascending.  Draws are with replacement and the set removes duplicates: the
+ *      reference's np.unique(concatenate(negCache, np.random.choice(potential_negatives, nNegSample))).  This is the
+ *      reference's ALGORITHM, not numpy's random stream.  A cache row outside neg_mask is still a candidate, as in the
+ *      reference.  nPot(i) = 0: no draws (the reference raises).  Bits are set with integer atomic OR: order-free.
+ *   b. Positive: kp2d_vpr_search_masked over pos_mask with k = 1 -> pos_idx [nq] int64 and the squared distance dPos2.
+ *      A query without a positive gets pos_idx = -1, neg_cnt = 0, d_pos = NaN and neg_idx all -1.
+ *   c. Negatives: kp2d_vpr_search_masked over cand with k = n_neg * n_neg_factor (ascending, padded).
+ *   d. Select: in float64, negative j violates when sqrt((double)dNeg2_j) < sqrt((double)dPos2) + sqrt((double)margin):
+ *      Euclidean distances and margin ** 0.5, as the reference compares them (:325).  The violators are a prefix of the
+ *      ascending list; the first n_neg of them -> neg_idx [nq, n_neg] int32 padded with -1, their number -> neg_cnt [nq]
+ *      int32 (0 is the reference's `return None`).  d_pos [nq] float = (float)sqrt((double)dPos2), Euclidean.
+ *      cand_mask [nq, W] or NULL: the candidate set of step a, for callers and tests.
+ *   scratch: kp2d_vpr_mine_scratch_bytes(nq, ndb, dim, n_neg, n_neg_factor) bytes (0: bad shape); a shorter one is
+ *     KP2D_ERR_ARG.
+ *   Accuracy: pos_idx and the negatives carry the masked search's contract; dPos2 and dNeg2 are its fp32 re-scores
+ *     (within 34 u d64, u = 2^-24), so d_pos is within 18 u d of the float64 Euclidean distance d (17 u from the square
+ *     root of 1 + 34 u, one u from rounding to float), and a negative can be classified differently from float64 only
+ *     when its distance lies within such a band of the threshold.
+ *   Determinism: no float atomics; the draws are a function of (seed, round, qid[i], j) and neg_mask[i] alone, the
+ *     searches are deterministic (above) and the selection is per query: every output is bit-identical from run to run,
+ *     and a query mined alone under its qid gets what it gets inside a batch. */
+#define KP2D_GEO_INVERT 1u
+int kp2d_geo_radius_mask(const double* db_xy, int64_t ndb, const double* q_xy, int nq, double radius, uint32_t flags,
+                         uint32_t* mask, int32_t* count, void* stream);
+int kp2d_mask_lists(const uint32_t* mask, int nq, int64_t ndb, const int64_t* lims, int64_t* idx, int64_t idx_len,
+                    int32_t* status, void* stream);
+size_t kp2d_vpr_mine_scratch_bytes(int nq, int64_t ndb, int dim, int n_neg, int n_neg_factor);
+int kp2d_vpr_mine(const void* packed_db, const float* db, int64_t ndb, int dim, const float* q, int nq,
+                  const int32_t* qid, const uint32_t* pos_mask, const uint32_t* neg_mask, const int32_t* neg_cache,
+                  int n_sample, int n_neg, int n_neg_factor, float margin, uint64_t seed, int round, uint32_t flags,
+                  int64_t* pos_idx, int32_t* neg_idx, int32_t* neg_cnt, float* d_pos, uint32_t* cand_mask, void* scratch,
+                  size_t scratch_bytes, void* stream);
 
 /* ---- k-means over descriptors (nano-vs-slam_amd/csrc/kmeans.hip) ------------------------------------------------
  * Replaces the faiss.Kmeans fit of the reference's NetVLAD initialisation (utils/netvlad_utils.py:83-88,

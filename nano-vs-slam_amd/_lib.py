@@ -111,6 +111,12 @@ SIGNATURES = {
     "kp2d_vpr_pack": (C.c_int, [_P, C.c_int64, C.c_int, _P, _P]),
     "kp2d_vpr_scratch_bytes": (C.c_size_t, [C.c_int, C.c_int64, C.c_int, C.c_int]),
     "kp2d_vpr_search": (C.c_int, [_P, _P, C.c_int64, C.c_int, _P, C.c_int, _P, C.c_int, C.c_uint32, _P, _P, _P, C.c_size_t, _P]),
+    "kp2d_vpr_search_masked": (C.c_int, [_P, _P, C.c_int64, C.c_int, _P, C.c_int, _P, C.c_int, C.c_uint32, _P, _P, _P, C.c_size_t, _P]),
+    "kp2d_geo_radius_mask": (C.c_int, [_P, C.c_int64, _P, C.c_int, C.c_double, C.c_uint32, _P, _P, _P]),
+    "kp2d_mask_lists": (C.c_int, [_P, C.c_int, C.c_int64, _P, _P, C.c_int64, _P, _P]),
+    "kp2d_vpr_mine_scratch_bytes": (C.c_size_t, [C.c_int, C.c_int64, C.c_int, C.c_int, C.c_int]),
+    "kp2d_vpr_mine": (C.c_int, [_P, _P, C.c_int64, C.c_int, _P, C.c_int, _P, _P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_float, C.c_uint64,
+                                C.c_int, C.c_uint32, _P, _P, _P, _P, _P, _P, C.c_size_t, _P]),
     "kp2d_kmeans_scratch_bytes": (C.c_size_t, [C.c_int64, C.c_int, C.c_int]),
     "kp2d_kmeans_step": (C.c_int, [_P, C.c_int64, C.c_int, _P, C.c_int, C.c_uint32, C.c_uint64, C.c_int, _P, _P, _P, _P, _P, _P,
                                    C.c_size_t, _P]),

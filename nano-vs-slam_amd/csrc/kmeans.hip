@@ -32,6 +32,7 @@
 #include "api_common.h"
 #include "device_guard.h"
 #include "kp2d_kernels.h"
+#include "mix64.h"
 
 using namespace kp2d;
 
@@ -264,11 +265,6 @@ __global__ __launch_bounds__(64) void km_update_kernel(const float* __restrict__
   }
 }
 
-__host__ __device__ inline uint64_t km_mix(uint64_t z) {
-  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-  z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-  return z ^ (z >> 31);
-}
 __host__ __device__ inline uint64_t km_draw(uint64_t seed, int iteration, int ci) {
   return km_mix(km_mix(seed + 0x9E3779B97F4A7C15ull) ^ (((uint64_t)(uint32_t)iteration << 32) | (uint32_t)ci));
 }

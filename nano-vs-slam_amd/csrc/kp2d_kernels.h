@@ -189,8 +189,9 @@ struct VprSearchArgs {
   int64_t ndb;
   int dim, nq, k, fp32;
   unsigned long long* codes;       // per-slice lists (scratch; set by launch_vpr_search)
+  const uint32_t* mask;            // [nq, ceil(ndb / 32)] row mask or null (kp2d_vpr_search_masked); not with limit
 };
-// (kmeans.hip searches with these two; the scratch is kp2d_vpr_scratch_bytes' for the same arguments)
+// (kmeans.hip and mining.hip search with these two; the scratch is kp2d_vpr_scratch_bytes' for the same arguments)
 int launch_vpr_pack(const float* x, int64_t n, int dim, void* packed, hipStream_t s);
 int launch_vpr_search(VprSearchArgs a, void* scratch, float* dist, int64_t* idx, hipStream_t s);
 

@@ -9,7 +9,9 @@
 //   vpr_search_kernel  64 queries x a slice of 128-row database tiles per workgroup.  Per tile: the 64 x 128 dot
 //                      products over dim on the matrix cores (K loop through LDS in 32-element chunks, two LDS buffers
 //                      filled by global_load_lds), key = |d|^2 - 2 q.d, then every query keeps its k best (key, row)
-//                      of the slice in a list of the scratch.  Nothing Q x N is written.
+//                      of the slice in a list of the scratch.  Nothing Q x N is written.  vpr_search_kernel<true> is the
+//                      masked form (kp2d_vpr_search_masked): a query sees the rows whose bit is set in its mask row, and
+//                      a tile whose mask words are zero for all 64 queries is skipped before its products
 //   vpr_merge_kernel   the k best of G slices' lists (bitonic sort in LDS), until one list per query is left
 //   vpr_final_kernel   the k finalists re-scored as sum (q - d)^2 in fp32 (fixed order), sorted by (distance, row)
 // Arithmetic of the key.  Default: split fp16, q.d = sum qh dh + qh dl + ql dh on v_mfma_f32_32x32x16_f16 with fp32
@@ -20,7 +22,8 @@
 // Determinism: a key depends on its query, its row and its tile's mode only (tiles are fixed 128-row blocks of the
 // database and slices are whole tiles), every reduction runs in a fixed order, and lists are cut by the total order of
 // (key, row).  A query's answer is therefore bit-identical for any batch of queries and any number of slices.
-// The entry points (kp2d_vpr_*, include/kp2d.h) are at the end of the file; kmeans.hip uses the two launchers directly.
+// The entry points (kp2d_vpr_*, include/kp2d.h) are at the end of the file; kmeans.hip and mining.hip use the two launchers
+// directly.
 #include <algorithm>
 #include <cfloat>
 #include <cstdint>
@@ -204,6 +207,9 @@ __device__ inline void tile_products(unsigned char* smem, const VprSearchArgs& a
   __syncthreads();                            // every wave is done with the buffers: the key tile may overwrite them
 }
 
+// MASKED: query i only sees the rows whose bit is set in a.mask[i] (kp2d_vpr_search_masked); the selecting thread tests
+// its query's bit where the unmasked form tests lim, and a tile none of the workgroup's queries has a row in is skipped
+template <bool MASKED>
 __global__ __launch_bounds__(256) void vpr_search_kernel(const VprSearchArgs a) {
   __shared__ __attribute__((aligned(16))) unsigned char smem[SMEM];   // one array: staging, key tile, tile norms
   float* s_key = reinterpret_cast<float*>(smem);
@@ -221,9 +227,10 @@ __global__ __launch_bounds__(256) void vpr_search_kernel(const VprSearchArgs a) 
   const bool selector = tid < QB && qs < a.nq;
   int lim = 0;
   if (selector) {
-    int64_t l = a.limit ? a.limit[qs] : a.ndb;
+    int64_t l = (!MASKED && a.limit) ? a.limit[qs] : a.ndb;
     lim = (int)(l < 0 ? 0 : (l > a.ndb ? a.ndb : l));
   }
+  const int64_t mw = (a.ndb + 31) >> 5;       // mask words per query
   if (tid == 0) *s_lim = 0;
   __syncthreads();
   if (selector && lim > 0) atomicMax(s_lim, lim);
@@ -238,6 +245,18 @@ __global__ __launch_bounds__(256) void vpr_search_kernel(const VprSearchArgs a) 
   for (int t = t_lo; t < t_hi; ++t) {
     const int64_t r0 = (int64_t)t * RB;
     if (r0 >= wg_lim) break;
+    unsigned m0 = 0, m1 = 0, m2 = 0, m3 = 0;  // the tile's four mask words of this thread's query (words past the row: 0)
+    if constexpr (MASKED) {
+      if (selector) {
+        const uint32_t* mq = a.mask + (int64_t)qs * mw;
+        const int64_t w0 = (int64_t)t * (RB / 32);
+        m0 = mq[w0];
+        if (w0 + 1 < mw) m1 = mq[w0 + 1];
+        if (w0 + 2 < mw) m2 = mq[w0 + 2];
+        if (w0 + 3 < mw) m3 = mq[w0 + 3];
+      }
+      if (!__syncthreads_or((m0 | m1 | m2 | m3) != 0)) continue;   // workgroup-uniform: no query has a row here
+    }
     int bad = 0;
     if (tid < RB) {
       const int64_t r = r0 + tid;
@@ -266,6 +285,10 @@ __global__ __launch_bounds__(256) void vpr_search_kernel(const VprSearchArgs a) 
     if (selector) {
       const int nrow = (int)min((int64_t)RB, (int64_t)lim - r0);
       for (int c = 0; c < nrow; ++c) {
+        if constexpr (MASKED) {
+          const unsigned w = c < 64 ? (c < 32 ? m0 : m1) : (c < 96 ? m2 : m3);
+          if (!((w >> (c & 31)) & 1u)) continue;
+        }
         const float key = s_key[tid * KP + c];
         if (key != key) continue;             // NaN (non-finite rows): never a neighbour
         const unsigned long long code = ((unsigned long long)fkey(key) << 32) | (unsigned)(r0 + c);
@@ -388,7 +411,9 @@ int launch_vpr_search(VprSearchArgs a, void* scratch, float* dist, int64_t* idx,
     return (int)hipGetLastError();
   }
   if (!a.fp32) hipLaunchKernelGGL(vpr_pack_kernel, dim3(a.nq), dim3(256), 0, s, a.q, a.dim, const_cast<unsigned char*>(a.qp));
-  hipLaunchKernelGGL(vpr_search_kernel, dim3((a.nq + QB - 1) / QB, p.nz), dim3(256), 0, s, a);
+  const dim3 grid((a.nq + QB - 1) / QB, p.nz);
+  if (a.mask) hipLaunchKernelGGL(vpr_search_kernel<true>, grid, dim3(256), 0, s, a);
+  else hipLaunchKernelGGL(vpr_search_kernel<false>, grid, dim3(256), 0, s, a);
   unsigned long long* cur = a.codes;
   int nz = p.nz;
   while (nz > 1) {
@@ -430,9 +455,10 @@ size_t kp2d_vpr_scratch_bytes(int nq, int64_t ndb, int dim, int k) {
   return vpr_layout(nullptr, vpr_plan(nq, ndb, k), a).bytes;
 }
 
-int kp2d_vpr_search(const void* packed_db, const float* db, int64_t ndb, int dim, const float* q, int nq,
-                    const int64_t* limit, int k, uint32_t flags, float* dist, int64_t* idx, void* scratch,
-                    size_t scratch_bytes, void* stream) {
+// kp2d_vpr_search and kp2d_vpr_search_masked: one body (limit and mask never both)
+static int vpr_search_checked(const void* packed_db, const float* db, int64_t ndb, int dim, const float* q, int nq,
+                              const int64_t* limit, const uint32_t* mask, int k, uint32_t flags, float* dist, int64_t* idx,
+                              void* scratch, size_t scratch_bytes, void* stream) {
   if (int e = vpr_dim_check(dim)) return e;
   if (k < 1 || k > 1024) return fail(KP2D_ERR_ARG, "vpr_search: k = %d outside [1, 1024]", k);
   if (nq < 0 || ndb < 0) return fail(KP2D_ERR_ARG, "vpr_search: negative size");
@@ -447,10 +473,24 @@ int kp2d_vpr_search(const void* packed_db, const float* db, int64_t ndb, int dim
   DeviceGuard guard(q, (hipStream_t)stream);
   VprSearchArgs a{};
   a.dbp = static_cast<const unsigned char*>(packed_db);
-  a.db = db; a.q = q; a.limit = limit; a.ndb = ndb; a.dim = dim; a.nq = nq; a.k = k;
+  a.db = db; a.q = q; a.limit = limit; a.mask = mask; a.ndb = ndb; a.dim = dim; a.nq = nq; a.k = k;
   a.fp32 = (flags & KP2D_VPR_FP32) ? 1 : 0;
   if (int e = launch_vpr_search(a, scratch, dist, idx, (hipStream_t)stream)) return fail(KP2D_ERR_HIP, "vpr_search kernels: %d", e);
   return KP2D_OK;
+}
+
+int kp2d_vpr_search(const void* packed_db, const float* db, int64_t ndb, int dim, const float* q, int nq,
+                    const int64_t* limit, int k, uint32_t flags, float* dist, int64_t* idx, void* scratch,
+                    size_t scratch_bytes, void* stream) {
+  return vpr_search_checked(packed_db, db, ndb, dim, q, nq, limit, nullptr, k, flags, dist, idx, scratch, scratch_bytes, stream);
+}
+
+int kp2d_vpr_search_masked(const void* packed_db, const float* db, int64_t ndb, int dim, const float* q, int nq,
+                           const uint32_t* mask, int k, uint32_t flags, float* dist, int64_t* idx, void* scratch,
+                           size_t scratch_bytes, void* stream) {
+  if (nq > 0 && ndb > 0 && !mask) return fail(KP2D_ERR_ARG, "vpr_search_masked: null mask");
+  if ((uintptr_t)mask % 4) return fail(KP2D_ERR_ARG, "vpr_search_masked: mask must be 4-byte aligned");
+  return vpr_search_checked(packed_db, db, ndb, dim, q, nq, nullptr, mask, k, flags, dist, idx, scratch, scratch_bytes, stream);
 }
 
 }  // extern "C"

@@ -19,7 +19,8 @@ import zlib
 import numpy as np
 
 __all__ = ["spread_tensor", "spread_state_dict", "synthetic_frames", "seeded_linear_state_dict",
-           "trained_like_tensor", "trained_like_state_dict", "random_homographies", "homography_pairs"]
+           "trained_like_tensor", "trained_like_state_dict", "random_homographies", "homography_pairs", "vpr_struct",
+           "place_descriptors"]
 
 
 def _rng(seed: int, key: str) -> np.random.Generator:
@@ -181,3 +182,40 @@ def seeded_linear_state_dict(shapes: dict, seed: int = 4321) -> dict:
             v = g.standard_normal(shp) * gain / math.sqrt(shp[-1])
         out[k] = v.astype(np.float32)
     return out
+
+
+def vpr_struct(numDb: int, numQ: int, seed: int):
+    """The fields of the reference's ``dbStruct`` (src/data/pittsburgh.py parse_dbStruct) that ground truth and triplet
+    mining read, for a seeded synthetic route: ``utmDb`` [numDb, 2], ``utmQ`` [numQ, 2] float64 UTM metres, ``numDb``,
+    ``numQ``, ``posDistThr`` = 25, ``posDistSqThr`` = 625, ``nonTrivPosDistSqThr`` = 100.  The database runs along a
+    smoothly turning route, one frame every 4-8 m with a metre of lateral jitter; most queries sit 0-12 m beside a random
+    point of the route, every eighth one 40-200 m away from it (no positives)."""
+    from types import SimpleNamespace
+    g = np.random.default_rng([seed, 0x56505253])
+    step = g.uniform(4.0, 8.0, numDb)
+    heading = np.cumsum(g.normal(0.0, 0.06, numDb)) + g.uniform(0, 2 * np.pi)
+    route = np.cumsum(np.stack([step * np.cos(heading), step * np.sin(heading)], 1), 0)
+    origin = np.array([585000.0, 4477000.0])                 # UTM zone 17T, as the reference's Pittsburgh structs
+    utmDb = origin + route + g.normal(0.0, 1.0, (numDb, 2))
+    at = g.integers(0, numDb, numQ)
+    normal = np.stack([-np.sin(heading[at]), np.cos(heading[at])], 1)
+    off = g.uniform(0.0, 12.0, numQ) * g.choice([-1.0, 1.0], numQ)
+    far = np.arange(numQ) % 8 == 7
+    off[far] = g.uniform(40.0, 200.0, int(far.sum())) * g.choice([-1.0, 1.0], int(far.sum()))
+    utmQ = origin + route[at] + normal * off[:, None] + g.normal(0.0, 1.0, (numQ, 2))
+    return SimpleNamespace(utmDb=utmDb, utmQ=utmQ, numDb=int(numDb), numQ=int(numQ), posDistThr=25, posDistSqThr=625,
+                           nonTrivPosDistSqThr=100)
+
+
+def place_descriptors(xy, dim: int, seed: int, length_scale: float = 60.0, noise=0.3, noise_seed: int = 0) -> np.ndarray:
+    """Unit descriptors [n, dim] float32 that vary smoothly with position ``xy`` [n, 2]: random Fourier features
+    sqrt(2 / dim) cos(xy w + b) with w ~ N(0, 1 / length_scale^2) (two places length_scale apart are about as similar as
+    exp(-1/2)), plus N(0, noise^2 / dim) per component (``noise``: one value, or one per row), normalised.  ``seed`` fixes w and b (use one seed for a database
+    and its queries), ``noise_seed`` the noise (use different ones)."""
+    xy = np.asarray(xy, np.float64)
+    g = np.random.default_rng([seed, 0x52464631])
+    w = g.normal(0.0, 1.0 / length_scale, (2, dim))
+    b = g.uniform(0.0, 2 * np.pi, dim)
+    f = np.sqrt(2.0 / dim) * np.cos(xy @ w + b)
+    f = f + np.random.default_rng([seed, noise_seed, 0x4E4F4953]).normal(0.0, 1.0 / np.sqrt(dim), f.shape) * np.reshape(noise, (-1, 1))
+    return (f / np.linalg.norm(f, axis=1, keepdims=True)).astype(np.float32)

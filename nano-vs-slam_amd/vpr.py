@@ -1,7 +1,7 @@
 """Place recognition on the device — the retrieval step behind the global descriptor (`vlad`).
 
 * ``FlatL2Index`` — faiss.IndexFlatL2's surface (``d``, ``ntotal``, ``add``, ``search``, ``reset``) on the HIP kernels of
-  csrc/vpr.hip (kp2d_vpr_pack / kp2d_vpr_search, include/kp2d.h): exact brute-force squared L2, the database resident in
+  csrc/vpr.hip (kp2d_vpr_pack / kp2d_vpr_search / kp2d_vpr_search_masked, include/kp2d.h): exact brute-force squared L2, the database resident in
   HBM, a fused top-k that never writes the Q x N distance matrix.
 * ``recall_at_n`` — Recall@N / AUC / MatchRatio exactly as the reference computes them
   (src/evaluation/global_descriptor.py:58-106), quirks included.
@@ -93,9 +93,13 @@ class FlatL2Index:
         _lib.check(lib.kp2d_vpr_pack(_ptr(self._x[self.ntotal:need]), n, self.d, _ptr(dst), _stream(self.device)))
         self.ntotal = need
 
-    def search(self, x, k: int, limit=None):
+    def search(self, x, k: int, limit=None, mask=None):
         """-> (D [nq, k] squared L2 distances, I [nq, k] row indices); numpy in -> numpy out (float32 / int64), device
-        tensors in -> device tensors out.  ``limit`` [nq] (optional): query i only sees rows [0, limit[i])."""
+        tensors in -> device tensors out.  ``limit`` [nq] (optional): query i only sees rows [0, limit[i]).  ``mask``
+        (optional, not with ``limit``): a mining.RowMask or a [nq, ceil(ntotal / 32)] int32 / uint32 device tensor of row
+        bits (include/kp2d.h, kp2d_vpr_search_masked): query i only sees the rows whose bit is set."""
+        if limit is not None and mask is not None:
+            raise ValueError("search takes limit or mask, not both")
         k = int(k)
         if k < 1 or k > MAX_K:
             raise ValueError(f"k = {k} outside [1, {MAX_K}]")
@@ -109,6 +113,14 @@ class FlatL2Index:
             lim = lim.to(self.device, torch.int64).contiguous().reshape(-1)
             if lim.numel() != nq:
                 raise ValueError(f"limit must have one entry per query ({nq}), got {lim.numel()}")
+        if mask is not None:
+            words = getattr(mask, "mask", mask)
+            if not isinstance(words, torch.Tensor):
+                raise TypeError("mask must be a RowMask or a device tensor")
+            _dev.require_device("search", words, None)
+            if words.dtype not in (torch.int32, torch.uint32) or tuple(words.shape) != (nq, (self.ntotal + 31) // 32):
+                raise ValueError(f"mask must be [{nq}, {(self.ntotal + 31) // 32}] int32 / uint32, got {words.dtype} {tuple(words.shape)}")
+            words = words.to(self.device).contiguous()
         D = torch.empty(nq, k, dtype=torch.float32, device=self.device)
         I = torch.empty(nq, k, dtype=torch.int64, device=self.device)
         if nq:
@@ -116,9 +128,10 @@ class FlatL2Index:
             nbytes = int(lib.kp2d_vpr_scratch_bytes(nq, self.ntotal, self.d, k))
             if self._scratch is None or self._scratch.numel() < nbytes:
                 self._scratch = _dev.scratch(nbytes, self.device)
-            _lib.check(lib.kp2d_vpr_search(_ptr(self._p) if self.ntotal else None, _ptr(self._x) if self.ntotal else None,
-                                           self.ntotal, self.d, _ptr(q), nq, _ptr(lim), k, PRECISIONS[self.precision],
-                                           _ptr(D), _ptr(I), _ptr(self._scratch), self._scratch.numel(), _stream(self.device)))
+            call, sel = (lib.kp2d_vpr_search, lim) if mask is None else (lib.kp2d_vpr_search_masked, words if self.ntotal else None)
+            _lib.check(call(_ptr(self._p) if self.ntotal else None, _ptr(self._x) if self.ntotal else None,
+                            self.ntotal, self.d, _ptr(q), nq, _ptr(sel), k, PRECISIONS[self.precision],
+                            _ptr(D), _ptr(I), _ptr(self._scratch), self._scratch.numel(), _stream(self.device)))
         if is_np:
             return D.cpu().numpy(), I.cpu().numpy()
         return D, I
