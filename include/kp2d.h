@@ -73,6 +73,14 @@ typedef struct kp2d_config {
 #define KP2D_FWD_ONLY_ENCODER 2u /* model.only_encoder(x) (kp2dtiny.py:515-518, vpr.py:78-89): backbone + convlad1-3 only;
                                     vlad = channel-wise L2-normalised encoder map [B,enc,Hc,Wc] (raw map when
                                     remove_netvlad); score/shift/feat/seg/depth are not written and may be NULL */
+#define KP2D_FWD_NO_SEG_LOGITS 4u /* the caller will not read seg: it wants the dense class ids this forward writes
+                                    (kp2d_set_seg_ids) and nothing else of the segmentation head.  Honoured only while
+                                    kp2d_set_seg_ids holds a buffer, ignored otherwise.  seg must still be a valid buffer
+                                    of the usual size; after the call its contents are UNSPECIFIED (big grids of the plain
+                                    V2 S configuration in f16x3 arithmetic skip the logits store and write ids only; every
+                                    other case — V3 / softmax, fp32 arithmetic, a tap set, small grids — runs as without
+                                    the flag and writes both).  The ids, and every other output, are the same bits either
+                                    way: the flag never changes a result, only whether the logits are stored */
 
 const char* kp2d_last_error(void);
 int32_t kp2d_abi_version(void);

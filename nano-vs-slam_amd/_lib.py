@@ -15,6 +15,7 @@ LIB_PATH = os.environ.get("KP2D_LIB") or os.path.join(_HERE, "csrc", "libkp2d_hi
 
 KP2D_FWD_EVAL = 1
 KP2D_FWD_ONLY_ENCODER = 2
+KP2D_FWD_NO_SEG_LOGITS = 4
 PRECISIONS = {"fp32": 0, "f16x3": 1}
 GLOBAL_DESCRIPTORS = {"netvlad": 0, "gem": 1, "convap": 2}
 UPSCALE_METHODS = {"pixelshuffle": 0, "convtranspose": 1}

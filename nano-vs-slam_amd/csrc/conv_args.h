@@ -28,6 +28,8 @@ enum Store : int {
   ST_MIX16 = 9,            // 64-channel groups below channel `nsplit`: fp32 NHWC into out0 (os0 channels); from `nsplit` on: the
                            // S16P tensor out1 (os1 channels, its chunk 0 = channel nsplit) — the heads' merged first layer, whose
                            // score / location slices are read by the fp32 dot-product kernels and the rest by split-fp16 convs
+  ST_IDS = 10,             // the layer's logits are NOT stored: only their per-pixel argmax, ids_out [B][H][W] int64 (out0 is left
+                           // untouched).  conv3x3_s16.hip's ids-only form behind a 64-channel S16P tensor; no other kernel takes it
 };
 // S16P ("split, planar rows"): an activation kept as the fp16 halves the split-fp16 kernels multiply, x = hi + lo with
 // hi = fp16(x), lo = fp16(x - hi) — per frame [C / 16 chunks][H][plane: hi | lo][W][16 halves], the same bytes as fp32 NHWC.
@@ -58,7 +60,7 @@ struct ConvArgs {
   const float* w_tr;                  // the 64-channel-group pack with the taps transposed (dy <-> dx), nullptr: none (conv3x3_wsm.hip: transposed tiles)
   int wsm_tr;                         // conv3x3_wsm.hip: tiles walk the map transposed (tile rows = map columns).  In: 0 never, 1 always, 2 where cheaper; the launcher hands the kernel its decision (0 / 1)
   int wsm_lanes;                      // stream lanes launching side by side (the form takes CUs / lanes workgroups)
-  long long* ids_out;                 // ST_NCHW, one channel group: also write argmax over the stored channels per pixel, [B][H][W] int64 (nullptr: no)
+  long long* ids_out;                 // ST_NCHW, one channel group: also write argmax over the stored channels per pixel, [B][H][W] int64 (nullptr: no); ST_IDS: the only output
   int ws_min;                         // least tiles for the warp-specialised conv1b form (0: 1024)
   int wsm_grid;                       // most workgroups per launch of the persistent forms; 0: automatic (conv_policy.h)
   // conv1b's warp-specialised form with conv1a computed by its staging waves (conv3x3_f16.hip STEM): the frames [B,3,H,W] and

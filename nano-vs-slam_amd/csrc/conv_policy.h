@@ -79,9 +79,16 @@ inline bool wsm_eligible(const ConvArgs& a, int N) {
   return true;
 }
 
-// conv3x3_s16.hip: 32-input-channel layers whose input is an S16P tensor, and the planar logits behind a 64-channel one
+// conv3x3_s16.hip: 32-input-channel layers whose input is an S16P tensor, and the planar logits (or only their argmax)
+// behind a 64-channel one
 inline bool s16_eligible(const ConvArgs& a) {
   if (a.taps != 9 || a.prec != 1 || a.in0.fmt != 1 || a.in1.c != 0 || a.in0.c != a.cin || a.in0.o != 0) return false;
+  if (a.store == ST_IDS) {
+    // class ids only (convs.8 under KP2D_FWD_NO_SEG_LOGITS): one 32-channel group of plain logits, a lane stores one pixel's id
+    if (a.cin != 64 || a.npad != 32 || a.cout < 1 || a.act != ACT_NONE || a.nsplit != a.cout || a.W < 32 || !a.ids_out) return false;
+    if (a.in0.bs != (long)a.H * a.W * a.cin || (long)a.H * a.W * a.cin * 4 >= BUF_LIMIT) return false;
+    return true;
+  }
   if (a.store == ST_NCHW) {
     // planar logits behind a 64-channel S16P tensor (confBb, convs.8): one 32-channel group, every channel into out0
     if (a.cin != 64 || a.npad != 32 || a.act != ACT_NONE || a.nsplit != a.cout || a.W < 32 || (a.W & 3) || a.ids_out) return false;
@@ -196,6 +203,9 @@ inline int choose_s16(const ConvArgs& a, int cus, ConvChoice& c) {
   c.grid = persistent_grid(c.nitems, cus, a.wsm_lanes, a.wsm_grid, a.s16_min);
   if (c.grid == 0) return -1006;
   c.form = FORM_S16;
+  // (ST_IDS: the launcher reports its variant itself, conv3x3_s16.hip.  The literals of this file are the forms
+  // tests/test_gpu_layer_fp64.py must reach with a plain forward; that one runs only under KP2D_FWD_NO_SEG_LOGITS and is
+  // checked bit for bit against the logits-writing forms by tests/test_gpu_seg_ids_only.py)
   c.variant = a.store == ST_NCHW ? "<s16>planar" : "<s16>";
   return 0;
 }
@@ -218,7 +228,8 @@ inline int choose_conv3x3_f16x3(const ConvArgs& a, int cus, ConvChoice& c) {
   c = ConvChoice{};
   auto general = [&c](int form, const char* variant) { c.form = form; c.variant = variant; return 0; };
   if (a.taps != 9 || a.prec != 1) return -1000;
-  if (a.in0.fmt == 1 && a.in1.c == 0 && (a.cin == 32 || a.store == ST_NCHW)) return choose_s16(a, cus, c);
+  if (a.in0.fmt == 1 && a.in1.c == 0 && (a.cin == 32 || a.store == ST_NCHW || a.store == ST_IDS)) return choose_s16(a, cus, c);
+  if (a.store == ST_IDS) return -1006;      // (the plan picks it only behind an S16P tensor)
   if (a.wsm_force) return choose_wsm(a, cus, 64, c);
   if (a.in0.fmt == 1 || a.in1.fmt == 1 || a.store == ST_S16P || a.store == ST_S16P_BOTH || a.store == ST_S16P_SHUFFLE || a.store == ST_MIX16) return -1006;
   if (a.store == ST_S16P_POOL) return ws_eligible(a, true) ? choose_ws(a, cus, true, c) : -1006;

@@ -33,6 +33,7 @@ int launch_conv3x3_f16x3_multi(const ConvArgs* list, int n, hipStream_t s);
 // conv3x3_wsm.hip / conv3x3_s16.hip: the persistent forms, launched as conv_policy.h chose them
 int launch_conv3x3_f16x3_wsm(const ConvArgs& a, const ConvChoice& c, hipStream_t s);
 int launch_conv3x3_f16x3_s16(const ConvArgs& a, const ConvChoice& c, hipStream_t s);
+int launch_conv3x3_f16x3_s16_ids(const ConvArgs& a, int grid, long nitems, hipStream_t s);   // its ST_IDS form (conv3x3_s16_ids.hip)
 // kp2d_set_tap on an S16P tensor: channels [c0, c0 + C) of a Ct-channel tensor -> planar fp32
 int launch_s16p_to_nchw(const float* in, float* out, int B, int C, int H, int W, int Ct, int c0, hipStream_t s);
 

@@ -77,6 +77,7 @@ Tuning tuning_from_env(const char* (*get)(const char*)) {
   t.lg_fuse = on("KP2D_LG_FUSE");
   t.lg_fuse_next = on("KP2D_LG_FUSE_NEXT");
   t.lg_tail_nw = (int)num("KP2D_LG_TAIL_NW", 0);
+  t.seg_ids_only = on("KP2D_SEG_IDS_ONLY");
   return t;
 }
 

@@ -105,6 +105,7 @@ struct Tuning {
   bool lg_fuse;       // KP2D_LG_FUSE=0: LightGlue block tails as separate linear launches
   bool lg_fuse_next;  // KP2D_LG_FUSE_NEXT=0: LightGlue projections as their own launches
   int lg_tail_nw;     // KP2D_LG_TAIL_NW=n: waves per workgroup of the LightGlue block tail (0: four)
+  bool seg_ids_only;  // KP2D_SEG_IDS_ONLY=0: KP2D_FWD_NO_SEG_LOGITS is ignored, the class logits are always stored (plan.cpp)
 };
 Tuning tuning_from_env(const char* (*get)(const char*));
 const Tuning& tuning();

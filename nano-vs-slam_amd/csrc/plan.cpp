@@ -56,9 +56,10 @@ const StoreKind kStore[] = {
     /* ST_S16P_BOTH    */ {SAME, 1, true, false},
     /* ST_S16P_SHUFFLE */ {SHUFFLED, 1, false, false},
     /* ST_MIX16        */ {SAME, 0, true, false},
+    /* ST_IDS          */ {SAME, 0, false, false},
 };
 static_assert(ST_NHWC == 0 && ST_NHWC_POOL == 1 && ST_NHWC_BOTH == 2 && ST_SHUFFLE == 3 && ST_NCHW == 4 && ST_S16P == 5 &&
-              ST_S16P_POOL == 6 && ST_S16P_BOTH == 7 && ST_S16P_SHUFFLE == 8 && ST_MIX16 == 9, "kStore is indexed by Store");
+              ST_S16P_POOL == 6 && ST_S16P_BOTH == 7 && ST_S16P_SHUFFLE == 8 && ST_MIX16 == 9 && ST_IDS == 10, "kStore is indexed by Store");
 
 // score / loc / depth heads: 1-4 output channels as an HBM-bound dot-product kernel (exact fp32 in both modes)
 bool head_dot(const ConvPack& c, int store, int concat_channels, int act) {
@@ -183,7 +184,7 @@ bool Plan::conv_args(const ConvPack& c, const ConvSrc& s0, const ConvSrc& s1, in
   const bool split = m->precision == KP2D_PREC_F16X3;
   a.dbg = m->dbg;
   a.prec = split ? 1 : 0;
-  a.ids_out = (store == ST_NCHW && seg_ids && o0.p && o0.p == seg_ptr && nsplit == c.cout && c.npad == 32) ? seg_ids : nullptr;
+  a.ids_out = ((store == ST_NCHW || store == ST_IDS) && seg_ids && o0.p && o0.p == seg_ptr && nsplit == c.cout && c.npad == 32) ? seg_ids : nullptr;
   a.wsm_min = m->wsm_min;
   a.wsm_grid = m->wsm_grid;
   a.wsm_tr = m->wsm_tr;
@@ -192,7 +193,7 @@ bool Plan::conv_args(const ConvPack& c, const ConvSrc& s0, const ConvSrc& s1, in
   a.s16_min = m->s16_min;
   // S16P tensors beyond the 32-channel stage are read and written by conv3x3_wsm.hip only: build() fixed the layout
   // after asking wsm_would_run (conv_policy.h), which then skips its item-count policy
-  a.wsm_force = ((s0.fmt == 1 && !(c.cin == 32 && s1.c == 0) && store != ST_NCHW) || store == ST_S16P_SHUFFLE || store == ST_MIX16 ||
+  a.wsm_force = ((s0.fmt == 1 && !(c.cin == 32 && s1.c == 0) && store != ST_NCHW && store != ST_IDS) || store == ST_S16P_SHUFFLE || store == ST_MIX16 ||
                  (store == ST_S16P && c.npad >= 64)) ? 1 : 0;
   if (stem_x && c.name == "backbone.conv1b") {
     a.stem_x = stem_x; a.stem_w = m->blob + m->conv1a_w; a.stem_scale = m->blob + m->conv1a_sc; a.stem_shift = m->blob + m->conv1a_sh;
@@ -237,8 +238,10 @@ void Plan::conv_src(const std::string& name, const ConvSrc& s0, const ConvSrc& s
                             : (c.taps == 9 ? (c.kc == 16 ? "conv3x3_f32<16>" : "conv3x3_f32<8>") : "conv1x1_f32");
     // conv1a computed inside conv1b's launch: its products count, its input is the 3-channel frame
     const bool stem = stem_x && name == "backbone.conv1b";
+    // (ST_IDS: the products are all there, the logits are not written — one int64 per pixel leaves)
+    const double out_bytes = store == ST_IDS ? 8.0 * px : 4.0 * px * c.cout;
     launch(name, fam, stem ? 2.0 * 9 * (3.0 * 16 + c.cin * c.cout) * px : 2.0 * c.taps * c.cin * c.cout * px,
-           stem ? 4.0 * px * (3 + c.cout / 4.0) + 4.0 * 9 * c.cin * c.cout : 4.0 * px * (c.cin + c.cout) + 4.0 * c.taps * c.cin * c.cout, [&] {
+           stem ? 4.0 * px * (3 + c.cout / 4.0) + 4.0 * 9 * c.cin * c.cout : 4.0 * px * c.cin + out_bytes + 4.0 * c.taps * c.cin * c.cout, [&] {
       if (!args()) return 0;
       const int e = launch_conv3x3(a, split ? 16 : c.kc, stream);
       if (m->profiling) m->prof[m->prof_used].kernel += conv3x3_last_variant();      // which tile form ran
@@ -498,6 +501,16 @@ void build(Plan& P, const FwdOut& o, uint32_t flags) {
   auto s16_planar = [&](int cout, bool with_ids = false) {
     return s16_all && !with_ids && cout <= 32 && m->c4 == 64 && m->c5 == 64 && !(W2 & 3);
   };
+  // KP2D_FWD_NO_SEG_LOGITS: the caller reads the class ids this forward writes (kp2d_set_seg_ids) and never the logits.
+  // Without the planar logits store the constraint above is gone: the last segmentation layer runs the TRANSPOSED products
+  // of conv3x3_s16.hip, where a lane holds eight channels of ONE pixel, finds the argmax in registers and stores 8 bytes
+  // per pixel instead of 4 n_classes (ST_IDS; 138 MB less per 64 frames of 240 x 320).  Same logits bit for bit, compared
+  // in the same order, so the ids are those of the other path.  Everything else — V3 / softmax, a tap (one launch per
+  // layer as planned without it), fp32 arithmetic, small grids, a layer the form does not take, KP2D_SEG_IDS_ONLY=0 (the
+  // A/B switch and the way back) — keeps writing both.
+  const ConvPack* seg_last = m->conv("seg_head.convs.8");
+  const bool seg_ids_only = (flags & KP2D_FWD_NO_SEG_LOGITS) && tuning().seg_ids_only && P.seg_ids && o.seg && !m->tap_dst && s16_planar(g.n_classes) &&
+                            g.n_classes >= 1 && seg_last && seg_last->npad == 32 && seg_last->cin == 64 && seg_last->cout == g.n_classes;
   Act mx{}, mxs{};
   int mx_split = 1 << 30;      // first channel of the merged layer kept in the S16P tensor mxs (s16_all: behind score | loc)
   if (merged && s16_all) {
@@ -734,7 +747,7 @@ void build(Plan& P, const FwdOut& o, uint32_t flags) {
     }
     Act g6 = upconv(L + std::to_string(i), hp + ".upsample2", g5);
     P.release(g5);
-    Act g7 = P.cbr(L + std::to_string(i + 1), g6, &skip, (hp == "seg_head" && s16_planar(g.n_classes, P.seg_ids != nullptr)) ? ST_S16P : ST_NHWC);
+    Act g7 = P.cbr(L + std::to_string(i + 1), g6, &skip, (hp == "seg_head" && (seg_ids_only || s16_planar(g.n_classes, P.seg_ids != nullptr))) ? ST_S16P : ST_NHWC);
     P.release(g6);
     *last = L + std::to_string(i + 2);
     return g7;
@@ -750,7 +763,7 @@ void build(Plan& P, const FwdOut& o, uint32_t flags) {
       const bool sm = (flags & KP2D_FWD_EVAL) && !g.remove_softmax;
       P.conv(last, g7, half, g7.C - half, nullptr, sm ? ACT_SOFTMAX_C : ACT_NONE, ST_NCHW, g.n_classes, H2, W2, {o.seg});
     } else {
-      P.conv(last, g7, g7.C, 0, nullptr, ACT_NONE, ST_NCHW, g.n_classes, H2, W2, {o.seg});
+      P.conv(last, g7, g7.C, 0, nullptr, ACT_NONE, (seg_ids_only && last == "seg_head.convs.8") ? ST_IDS : ST_NCHW, g.n_classes, H2, W2, {o.seg});
     }
     P.release(g7);
   }

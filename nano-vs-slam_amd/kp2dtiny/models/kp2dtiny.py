@@ -519,6 +519,10 @@ class _KP2DTinyBase(nn.Module):
     # ---- reference API ------------------------------------------------------------------------
     def forward(self, x):
         """Reference: KP2DTinyV2.forward kp2dtiny.py:552-591 / KP2DTinyV3.forward :906-957."""
+        return self._forward_input(x)
+
+    def _forward_input(self, x, drop_logits=False):
+        """forward(); ``drop_logits``: see _forward (the streaming entry points, whose callers never see ``seg``'s logits)."""
         c0 = 3 if getattr(self, "use_color", True) else 1
         if x.dim() != 4 or x.shape[1] != c0:
             raise ValueError(f"expected [B,{c0},H,W] input, got {tuple(x.shape)}")
@@ -526,13 +530,17 @@ class _KP2DTinyBase(nn.Module):
             raise TypeError("input must be float32")
         x = x.contiguous()
         B, _, H, W = x.shape
-        return self._forward(x.device, B, H, W, x=x)
+        return self._forward(x.device, B, H, W, x=x, drop_logits=drop_logits)
 
     def forward_frames(self, frames, size=None):
         """forward() straight from uint8 frames [B,Hs,Ws,3] on the device: /255, the bilinear resize to ``size`` = (H, W)
         and .sub(0.5).mul(2) (src/evaluation/visual_odometry.py:77-87) run as the first layer's prologue
         (kp2d_forward_frames): the float input tensor is never materialised.  Bit-identical to
         forward(pipeline.frames_to_input(frames, device, size))."""
+        return self._forward_uint8(frames, size)
+
+    def _forward_uint8(self, frames, size=None, drop_logits=False):
+        """forward_frames(); ``drop_logits``: see _forward."""
         if frames.dim() != 4 or frames.shape[-1] != 3 or frames.dtype != torch.uint8:
             raise ValueError("expected uint8 frames of shape [B,Hs,Ws,3]")
         if frames.device.type != "cuda":
@@ -540,9 +548,13 @@ class _KP2DTinyBase(nn.Module):
         frames = frames.contiguous()
         B, Hs, Ws, _ = frames.shape
         H, W = (Hs, Ws) if size is None else (int(size[0]), int(size[1]))
-        return self._forward(frames.device, B, H, W, frames=frames)
+        return self._forward(frames.device, B, H, W, frames=frames, drop_logits=drop_logits)
 
-    def _forward(self, dev, B, H, W, x=None, frames=None):
+    def _forward(self, dev, B, H, W, x=None, frames=None, drop_logits=False):
+        """``drop_logits``: the caller hands the returned dict straight to post_processing, which replaces ``seg`` by the class
+        ids this forward wrote and never reads the logits (the identity / version check there).  Where the forward writes
+        those ids it is then told so (KP2D_FWD_NO_SEG_LOGITS): the last segmentation layer may skip its logits store, and
+        ``seg``'s contents are unspecified.  Private: a public forward returns real logits."""
         eng = self._get_engine(dev)
         self._warn_if_training_semantics_expected()
         q = 2 * self.cell    # the segmentation head pools the cell grid once more
@@ -568,12 +580,16 @@ class _KP2DTinyBase(nn.Module):
         if not self.training and not self.sample_segmentation and os.environ.get("KP2D_FUSED_ARGMAX", "1") != "0":
             ids = torch.empty(B, 1, H2, W2, dtype=torch.int64, device=dev)
             _lib.check(eng.lib.kp2d_set_seg_ids(eng.handle, _ptr(ids), ids.numel()))
+            if drop_logits:
+                flags |= _lib.KP2D_FWD_NO_SEG_LOGITS
         try:
             self._run_forward(eng, x, frames, B, H, W, flags, score, shift, feat, seg, vlad, depth, ws, stream)
         finally:
             if ids is not None:
                 eng.lib.kp2d_set_seg_ids(eng.handle, None, 0)
         self.__dict__["_seg_ids_cache"] = (weakref.ref(seg), seg._version, ids) if ids is not None else None
+        if flags & _lib.KP2D_FWD_NO_SEG_LOGITS:
+            seg._kp2d_logits_dropped = True      # (travels with the tensor object: post_processing below)
         out = {"score": score, "coord": shift, "feat": feat, "vlad": vlad, "seg": seg}
         if self.depth:
             out["depth"] = depth        # already sigmoid (kp2dtiny.py:588-590 / :955-956)
@@ -614,6 +630,9 @@ class _KP2DTinyBase(nn.Module):
                     and seg._version == cache[1] and tuple(cache[2].shape) == (B, 1, Hs, Ws)):
                 seg_ids, seg = cache[2], None
             else:
+                if getattr(out["seg"], "_kp2d_logits_dropped", False):     # (never a quiet argmax over an unwritten tensor)
+                    raise RuntimeError("post_processing: this forward was told to drop the class logits (drop_logits) and its "
+                                       "class ids are gone: post-process the dict the forward returned, once, unmodified")
                 seg_ids = (torch.empty(B, 1, Hc, Wc, dtype=torch.int64, device=dev) if self.sample_segmentation
                            else torch.empty(B, 1, Hs, Ws, dtype=torch.int64, device=dev))
         _lib.check(eng.lib.kp2d_post(eng.handle, _ptr(score), _ptr(shift), _ptr(feat), _ptr(seg), B, int(H), int(W),

@@ -52,6 +52,17 @@ def _fused_front(net) -> bool:
             and hasattr(net, "forward_frames") and int(net.channel_dims[0]) == 16)
 
 
+def _stream_forward(net, x=None, frames=None, size=None):
+    """The forward of the entry points that post-process inside this module: ``seg``'s logits never reach the caller, so
+    the engine is told it may skip their store (kp2dtiny._forward ``drop_logits``).  The result goes to post_processing as
+    it is.  Models without that private entry (anything that is not a KP2DTiny host mirror) run their public forward."""
+    if frames is not None:
+        f = getattr(net, "_forward_uint8", None)
+        return f(frames, size, drop_logits=True) if f is not None else net.forward_frames(frames, size)
+    f = getattr(net, "_forward_input", None)
+    return f(x, drop_logits=True) if f is not None else net(x)
+
+
 def frames_to_input(frames, device, size=None) -> torch.Tensor:
     """uint8 [Hs,Ws,3] / [B,Hs,Ws,3] (numpy or torch) -> float32 [B,3,H,W] in [-1,1] on ``device``;
     ``size`` = (H, W) resizes (visual_odometry.py:77-87: /255, kornia resize, .sub(0.5).mul(2))."""
@@ -80,11 +91,11 @@ def inference(net, image, new_size=None, nn_thresh=0.7, top_k=4000, device="cuda
         # uint8 frames straight into the first layer (kp2d_forward_frames): no float frame in between
         t = _frames_on_device(image, device)
         H, W = (t.shape[1], t.shape[2]) if new_size is None else (int(new_size[0]), int(new_size[1]))
-        out = net.forward_frames(t, (H, W))
+        out = _stream_forward(net, frames=t, size=(H, W))
     else:
         x = frames_to_input(image, device, new_size)
         _, _, H, W = x.shape
-        out = net(x)
+        out = _stream_forward(net, x=x)
     out = net.post_processing(out, H, W)
     scale = None
     if new_size is not None and (H, W) != src_hw:     # pts / scale: visual_odometry.py:81-83, 119-121
@@ -225,14 +236,14 @@ class FrameStream:
         with eng.using_workspace(self._slot_ws[slot]):
             if _fused_front(self.net) and not self.zero_copy:
                 # frame in device memory: the first layer reads it (kp2d_forward_frames)
-                fwd = self.net.forward_frames(self.dev_in[slot], (self.H, self.W))
+                fwd = _stream_forward(self.net, frames=self.dev_in[slot], size=(self.H, self.W))
             else:
                 # zero-copy slot (pinned host memory): ONE pass over PCIe by the preprocess kernel; the fused first layer
                 # would fetch every halo / bilinear tap across the bus again
                 x = torch.empty(1, 3, self.H, self.W, device=self.dev)
                 Hs, Ws = self.dev_in[slot].shape[1:3]
                 _lib.check(lib.kp2d_preprocess(_ptr(self.dev_in[slot]), 1, Hs, Ws, _ptr(x), self.H, self.W, _stream(self.dev)))
-                fwd = self.net(x)
+                fwd = _stream_forward(self.net, x=x)
         out = self.net.post_processing(fwd, self.H, self.W)
         from .selectors import _cap, select_and_gather
         idx, _val, cnt, pts, dsel = select_and_gather(out["score"], out["coord"], out["feat"], _cap(self.top_k, out["score"]),
@@ -509,7 +520,7 @@ class BatchStream:
             self._ws[slot] = _dev.scratch(need, self.dev)
         with torch.cuda.stream(st), torch.no_grad(), self._eng.using_workspace(self._ws[slot]):
             x.record_stream(st)
-            out = self.net.post_processing(self.net(x), H, W)
+            out = self.net.post_processing(_stream_forward(self.net, x=x), H, W)
             if self.select:
                 _idx, _val, cnt, pts, desc = select_and_gather(out["score"], out["coord"], out["feat"],
                                                                _cap(self.top_k, out["score"]), self.thr)
@@ -554,11 +565,11 @@ class BatchStream:
                     t = t.to(self.dev, non_blocking=True)
                 x = torch.empty(B, 3, H, W, device=self.dev)
                 _lib.check(_lib.load().kp2d_preprocess(_ptr(t), B, Hs, Ws, _ptr(x), H, W, _stream(self.dev)))
-                fwd = self.net(x)
+                fwd = _stream_forward(self.net, x=x)
             else:
                 # pageable frames: torch's staged upload on this slot's stream, then straight into the first layer
                 # (kp2d_forward_frames) — what inference() does, with the other slots' kernels running meanwhile
-                fwd = self.net.forward_frames(t.to(self.dev, non_blocking=True), (H, W))
+                fwd = _stream_forward(self.net, frames=t.to(self.dev, non_blocking=True), size=(H, W))
             out = self.net.post_processing(fwd, H, W)
             _idx, _val, cnt, pts, desc = select_and_gather(out["score"], out["coord"], out["feat"],
                                                            _cap(self.top_k, out["score"]), self.thr)

@@ -1,7 +1,10 @@
 #!/usr/bin/env python3
 """Per-layer HIP-event profile of one forward (uses the engine's kp2d_profile_* hooks).
 
-    python3 tools/layer_profile.py [--config S] [--v3] [--batch 64] [--height 240] [--width 320] [--chunk 0]
+    python3 tools/layer_profile.py [--config S] [--v3] [--batch 64] [--height 240] [--width 320] [--chunk 0] [--streaming]
+
+--streaming: the plan pipeline.BatchStream / FrameStream / inference() run (the forward is told that nobody reads the class
+logits, kp2dtiny._forward drop_logits); without it the plan of a public model(x).
 """
 import argparse
 import ctypes as C
@@ -25,6 +28,7 @@ def main():
     ap.add_argument("--chunk", type=int, default=0)
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--precision", default="f16x3")
+    ap.add_argument("--streaming", action="store_true", help="profile the streaming entry points' plan (class ids without logits)")
     a = ap.parse_args()
     from nano_vs_slam_amd.kp2dtiny.models.kp2dtiny import tiny_factory
     from nano_vs_slam_amd.synthetic import spread_state_dict
@@ -35,9 +39,14 @@ def main():
     model.set_precision(a.precision)
     model.training = False
     x = torch.rand(a.batch, 3, a.height, a.width, device="cuda:0") * 2 - 1
+    if a.streaming:
+        plain = model
+
+        def model(t):
+            return plain._forward_input(t, drop_logits=True)
     with torch.no_grad():
         model(x)
-        eng = model._engine
+        eng = (plain if a.streaming else model)._engine
         lib = eng.lib
         if a.chunk:
             lib.kp2d_set_chunk_frames(eng.handle, a.chunk)
