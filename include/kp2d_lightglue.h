@@ -3,8 +3,9 @@
  * Replaces, for inference, the reference's `LightGlue(conf, weights_path)` torch module
  * (lightglue/lightglue.py:418-614; constructed at src/visual_odometry/visual_odometry.py:149-155 and by
  * gluefactory's `matchers.lightglue`, gluefactory/configs/kp2dtiny_S+lightglue_homography.yaml:25-31): eval mode,
- * flash = False, depth_confidence = width_confidence = -1 (the reference configs' values; early stopping and point
- * pruning are not built and the host layer refuses them).
+ * flash = False, depth_confidence = -1 (the reference configs' value; early stopping is not built and the host layer
+ * refuses it — the reference cannot run it either, lightglue.py:624/636).  Point pruning (width_confidence > 0,
+ * lightglue.py:535-545, :564-579, :585-597, :618-625) is kp2d_lg_forward_pruned below.
  *
  * Conventions are those of include/kp2d.h: plain pointers and sizes, device pointers for tensors, caller-provided
  * workspace, work enqueued on the caller's stream, int status (0 = OK, kp2d_status codes, kp2d_last_error()).
@@ -70,6 +71,34 @@ int kp2d_lg_forward_counts(kp2d_lg* m, const float* kpts0, const float* kpts1, c
                            float filter_threshold, float* log_assignment, int64_t* matches0, int64_t* matches1,
                            float* mscores0, float* mscores1, float* ref_desc0, float* ref_desc1, void* workspace,
                            size_t workspace_bytes, void* stream);
+
+/* Point pruning (width_confidence > 0 in eval mode).  After every layer but the last, and for each set, a point stays iff
+ * sigmoid(log_assignment[i].matchability(desc)) > 1 - width_confidence (get_pruning_mask :618-625 without token confidences:
+ * early stopping is off); the survivors keep their ascending order, and the later layers, the assignment and filter_matches
+ * see only them.  The reference asserts B == 1; here every pair of the batch is pruned on its own and its result is that of
+ * its B == 1 call.  The sets stay PADDED (static shapes): pruning compacts the surviving rows to the front of each set and
+ * lowers the per-pair counts on the device, exactly the padded-set convention of kp2d_lg_forward_counts.
+ *   n0 / n1 may be NULL: every pair starts with M / N points (then size0 / size1 may be NULL too).
+ *   matches0/1, mscores0/1 are in the ORIGINAL index space; pruned and padding rows get -1 / 0.
+ *   log_assignment [B,M+1,N+1] and ref_desc0/1 are in SURVIVOR order: inner entries (j < nkeep0[b], l < nkeep1[b]) are
+ *     valid, the other inner entries -inf, the dustbin column N / row M holds the survivors' entries, the rest is unspecified
+ *     (as in kp2d_lg_forward_counts).
+ *   keep0 [B,M] / keep1 [B,N] int32: original index of survivor j, ascending; -1 past the count.
+ *   nkeep0 / nkeep1 [B] int32: survivors of each pair.
+ *   prune0 [B,M] / prune1 [B,N] int64, original index space: a point dropped after layer i holds i + 1, a survivor
+ *     n_layers (lightglue.py:543-544, :572), a padding row 0.
+ * A pair one of whose sets becomes (or starts) empty has matches -1 and scores 0; its other outputs are unspecified (they
+ * may be NaN) and nothing of it reaches another pair.  (The reference fails there: max over an empty dimension.)
+ * width_confidence outside (0, 1] -> KP2D_ERR_ARG; a null output other than ref_desc0/1 -> KP2D_ERR_ARG; a workspace below
+ * kp2d_lg_workspace_bytes_pruned -> KP2D_ERR_WORKSPACE.  No host synchronisation, no allocation: the call can be captured
+ * into a HIP graph. */
+size_t kp2d_lg_workspace_bytes_pruned(const kp2d_lg* m, int B, int M, int N);
+int kp2d_lg_forward_pruned(kp2d_lg* m, const float* kpts0, const float* kpts1, const float* desc0, const float* desc1,
+                           const float* size0, const float* size1, const int32_t* n0, const int32_t* n1, int B, int M, int N,
+                           float filter_threshold, float width_confidence, float* log_assignment, int64_t* matches0,
+                           int64_t* matches1, float* mscores0, float* mscores1, float* ref_desc0, float* ref_desc1,
+                           int32_t* keep0, int32_t* keep1, int32_t* nkeep0, int32_t* nkeep1, int64_t* prune0, int64_t* prune1,
+                           void* workspace, size_t workspace_bytes, void* stream);
 
 #ifdef __cplusplus
 }

@@ -2,4 +2,4 @@
 
     from lightglue.lightglue import LightGlue
 """
-from nano_vs_slam_amd.lightglue.lightglue import LightGlue, __main_model__  # noqa: F401
+from nano_vs_slam_amd.lightglue.lightglue import LightGlue, __main_model__, unpad_pruned  # noqa: F401

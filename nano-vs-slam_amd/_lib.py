@@ -141,6 +141,9 @@ SIGNATURES = {
     "kp2d_lg_workspace_bytes": (C.c_size_t, [_P, C.c_int, C.c_int, C.c_int]),
     "kp2d_lg_forward": (C.c_int, [_P] + [_P] * 6 + [C.c_int] * 3 + [C.c_float] + [_P] * 7 + [_P, C.c_size_t, _P]),
     "kp2d_lg_forward_counts": (C.c_int, [_P] + [_P] * 8 + [C.c_int] * 3 + [C.c_float] + [_P] * 7 + [_P, C.c_size_t, _P]),
+    "kp2d_lg_workspace_bytes_pruned": (C.c_size_t, [_P, C.c_int, C.c_int, C.c_int]),
+    "kp2d_lg_forward_pruned": (C.c_int, [_P] + [_P] * 8 + [C.c_int] * 3 + [C.c_float] * 2 + [_P] * 7 + [_P] * 6 +
+                               [_P, C.c_size_t, _P]),
 }
 
 _lib = None

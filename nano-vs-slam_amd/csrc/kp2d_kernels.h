@@ -177,8 +177,26 @@ struct LgAssignArgs {
   float th;                                 // filter_threshold
   const int32_t* cnt0 = nullptr; const int32_t* cnt1 = nullptr;   // [B] keypoints that exist in each set (rows past them are padding), null: M / N
   int64_t* matches0; int64_t* matches1; float* mscores0; float* mscores1;
+  // point pruning: rows are survivors; row e of set 0 is original keypoint ind0[b][e] (ind1 alike).  Matches and scores
+  // are scattered to the original positions (the caller has filled the outputs with -1 / 0).  null: identity
+  const int32_t* ind0 = nullptr; const int32_t* ind1 = nullptr;
 };
 int launch_lg_assign(const LgAssignArgs& a, hipStream_t s);
+
+// point pruning between layers (lightglue.py:564-579): the rows of every sequence whose matchability score
+// sigmoid(w . x + bias) exceeds thr move to the front of the sequence, in order; cnt becomes the survivors' number
+struct LgPruneArgs {
+  float* x; float* cs;                      // [B*M + B*N][D] descriptors / [..][hd] cos | sin, compacted in place
+  const float* w;                           // log_assignment[i].matchability: weight [D], bias at w[D]
+  int32_t* cnt;                             // [2B] rows that exist in each sequence ([set 0 | set 1]), updated
+  int32_t* ind0; int32_t* ind1;             // [B][M] / [B][N] original index of row j (-1 past the count), compacted
+  int64_t* prune0; int64_t* prune1;         // [B][M] / [B][N] by ORIGINAL index: += 1 for every survivor
+  int B, M, N, D, hd;
+  float thr;                                // 1 - width_confidence
+};
+// cnt <- n0 | n1 clamped to [0, M] / [0, N] (null: M / N), ind <- 0..cnt-1 then -1, prune <- 1 (padding rows 0)
+int launch_lg_prune_init(const LgPruneArgs& a, const int32_t* n0, const int32_t* n1, hipStream_t s);
+int launch_lg_prune(const LgPruneArgs& a, hipStream_t s);
 
 // ---- vpr.hip: flat squared-L2 top-k over global descriptors (kp2d_vpr_*) ----------------------
 struct VprSearchArgs {

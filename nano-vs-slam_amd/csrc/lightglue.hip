@@ -1,6 +1,6 @@
-// LightGlue matcher kernels (reference: lightglue/lightglue.py; inference path, flash = False, no early stopping /
-// point pruning).  Descriptor width D <= 64 (configs S / A: 32, F: 64), 4 heads, <= 1024 keypoints per image: the
-// whole matcher is ~2 GFLOP per image pair and launch/latency bound (23 launches of 5-34 us per forward).  The kernels
+// LightGlue matcher kernels (reference: lightglue/lightglue.py; inference path, flash = False, no early stopping;
+// point pruning is a row compaction between layers, lg_prune_kernel).  Descriptor width D <= 64 (configs S / A: 32,
+// F: 64), 4 heads, <= 1024 keypoints per image: the whole matcher is ~2 GFLOP per image pair and launch/latency bound (23 launches of 5-34 us per forward).  The kernels
 // are row-wise: both images' tokens live in ONE row-major buffer [B*M rows of image 0 | B*N rows of image 1] so that
 // every per-token layer (Linear, rotary, LayerNorm, GELU, residual) is a single launch over all tokens of the batch.
 // D = 32: the token-wise products run on the matrix cores in split-fp16 (fp32-grade, as the attention products of
@@ -14,7 +14,8 @@
 //  (attention)          attention.hip: softmax(q k^T / sqrt(d)) v, streaming, split-fp16 matrix cores (:208-224, :312-321)
 //  lg_sim_kernel        sim = f0 f1^T (:391) + per-tile row / column log-sum-exp partials
 //  lg_finalize_kernel   sigmoid_log_double_softmax (:363-376) + per-tile row / column max, argmax (filter_matches :403-404)
-//  lg_filter_kernel     mutual check, threshold, match scores (:405-416)
+//  lg_filter_kernel     mutual check, threshold, match scores (:405-416); with pruning, scattered to original indices (:586-594)
+//  lg_prune_kernel      width_confidence > 0: matchability score, ordered compaction of the survivors (:564-579)
 #include "kp2d_kernels.h"
 #include "device_guard.h"
 #include "options.h"
@@ -748,6 +749,35 @@ __global__ __launch_bounds__(256) void lg_filter_kernel(const LgAssignArgs a) {
     return best_of_partials(a.cmax + (size_t)b * TM * N + j, a.carg + (size_t)b * TM * N + j, TM, N, mx);
   };
   const int Mv = a.cnt0 ? min(M, a.cnt0[b]) : M, Nv = a.cnt1 ? min(N, a.cnt1[b]) : N;
+  if (a.ind0) {
+    // point pruning: rows / columns are survivors; results go to their original positions, partners are named by their
+    // original indices (lightglue.py:586-594).  Everything else keeps the caller's -1 / 0 fill.
+    const int32_t* i0 = a.ind0 + (size_t)b * M;
+    const int32_t* i1 = a.ind1 + (size_t)b * N;
+    if (Mv == 0 || Nv == 0) return;
+    if (e < Mv) {
+      float mx;
+      const int j = row_best(e, mx);
+      const bool mutual = col_best(j) == e;
+      const float ms = mutual ? expf(mx) : 0.f;
+      const int o = i0[e];
+      if ((unsigned)o < (unsigned)M) {
+        a.mscores0[(size_t)b * M + o] = ms;
+        a.matches0[(size_t)b * M + o] = (mutual && ms > a.th && j < Nv) ? (int64_t)i1[j] : (int64_t)-1;
+      }
+    } else if (e >= M && e - M < Nv) {
+      const int j = e - M, i = col_best(j);
+      float mx;
+      const bool mutual1 = row_best(i, mx) == j;
+      const float ms0 = mutual1 ? expf(mx) : 0.f;
+      const int o = i1[j];
+      if ((unsigned)o < (unsigned)N) {
+        a.mscores1[(size_t)b * N + o] = ms0;
+        a.matches1[(size_t)b * N + o] = (mutual1 && ms0 > a.th && i < Mv) ? (int64_t)i0[i] : (int64_t)-1;
+      }
+    }
+    return;
+  }
   if (e < M && (e >= Mv || Nv == 0)) {              // a padding row, or nothing to match against
     a.mscores0[(size_t)b * M + e] = 0.f;
     a.matches0[(size_t)b * M + e] = -1;
@@ -769,6 +799,111 @@ __global__ __launch_bounds__(256) void lg_filter_kernel(const LgAssignArgs a) {
     a.mscores1[(size_t)b * N + j] = ms0;
     a.matches1[(size_t)b * N + j] = (mutual1 && ms0 > a.th) ? (int64_t)i : (int64_t)-1;
   }
+}
+
+// ---------------------------------------------------------------------------------------------
+// Point pruning (lightglue.py:564-579, get_pruning_mask :618-625 without token confidences, get_matchability :395-396).
+// One workgroup per sequence ([set 0 | set 1], 2B of them) walks the sequence's rows in ascending chunks of 256, one
+// row per thread: score, ordered exclusive scan of the keep flags (wave ballot + popcount, wave totals through LDS — no
+// atomics, the survivors keep their order as torch.where gives it), then the row, its cos | sin row and its original
+// index move to the front.
+// ---------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void lg_prune_init_kernel(const LgPruneArgs a, const int32_t* n0, const int32_t* n1) {
+  const int s = blockIdx.x, set = s >= a.B, b = set ? s - a.B : s, cap = set ? a.N : a.M;
+  const int32_t* n = set ? n1 : n0;
+  const int cnt = n ? max(0, min(cap, n[b])) : cap;
+  int32_t* ind = (set ? a.ind1 : a.ind0) + (size_t)b * cap;
+  int64_t* pr = (set ? a.prune1 : a.prune0) + (size_t)b * cap;
+  for (int j = threadIdx.x; j < cap; j += 256) {
+    ind[j] = j < cnt ? j : -1;
+    pr[j] = j < cnt ? 1 : 0;          // prune starts at ones (:543-544); a padding row is no point
+  }
+  if (threadIdx.x == 0) a.cnt[s] = cnt;
+}
+
+template <int D>
+__global__ __launch_bounds__(256) void lg_prune_kernel(const LgPruneArgs a) {
+  __shared__ float wv[D + 1];
+  __shared__ int wtot[4];
+  const int s = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int set = s >= a.B, b = set ? s - a.B : s, cap = set ? a.N : a.M;
+  const size_t r0 = set ? (size_t)a.B * a.M + (size_t)b * a.N : (size_t)b * a.M;
+  float* X = a.x + r0 * D;
+  float* CS = a.cs + r0 * a.hd;
+  int32_t* IND = (set ? a.ind1 : a.ind0) + (size_t)b * cap;
+  int64_t* PR = (set ? a.prune1 : a.prune0) + (size_t)b * cap;
+  const int cnt = max(0, min(cap, a.cnt[s]));
+  const int hq = a.hd >> 2;                  // 16-byte granules of a cos | sin row (<= 4)
+  if (tid <= D) wv[tid] = a.w[tid];
+  __syncthreads();
+  int kept = 0;
+  // In place: a row's destination is never past its source (destination = survivors before it), the chunks ascend and
+  // a chunk is read completely (registers) before the barrier that precedes its stores, so no store lands on a row
+  // that is still to be read; and this workgroup alone owns the sequence, its count included, for the whole launch.
+  for (int c0 = 0; c0 < cnt; c0 += 256) {
+    const int r = c0 + tid;
+    const bool ex = r < cnt;
+    float4 xr[D / 4], ca{}, cb{}, cc{}, cd{};      // (the cos | sin row as four named granules: an array indexed
+                                                   // under `q < hq` is moved to LDS by the compiler, 16 KB of it)
+    int ind = -1;
+    float z = wv[D];
+    if (ex) {
+#pragma unroll
+      for (int q = 0; q < D / 4; ++q) xr[q] = *reinterpret_cast<const float4*>(X + (size_t)r * D + 4 * q);
+      const float4* cp = reinterpret_cast<const float4*>(CS + (size_t)r * a.hd);
+      ca = cp[0];
+      if (hq > 1) cb = cp[1];
+      if (hq > 2) cc = cp[2];
+      if (hq > 3) cd = cp[3];
+      ind = IND[r];
+#pragma unroll
+      for (int q = 0; q < D / 4; ++q) {
+        z = fmaf(xr[q].x, wv[4 * q], z); z = fmaf(xr[q].y, wv[4 * q + 1], z);
+        z = fmaf(xr[q].z, wv[4 * q + 2], z); z = fmaf(xr[q].w, wv[4 * q + 3], z);
+      }
+    }
+    const bool keep = ex && 1.f / (1.f + expf(-z)) > a.thr;      // (a NaN score is no survivor)
+    const unsigned long long bal = __ballot(keep);
+    if (lane == 0) wtot[wave] = __popcll(bal);
+    __syncthreads();
+    int dst = kept + __popcll(bal & ((1ull << lane) - 1ull));
+    for (int w = 0; w < wave; ++w) dst += wtot[w];
+    kept += wtot[0] + wtot[1] + wtot[2] + wtot[3];
+    if (keep) {
+#pragma unroll
+      for (int q = 0; q < D / 4; ++q) *reinterpret_cast<float4*>(X + (size_t)dst * D + 4 * q) = xr[q];
+      float4* cp = reinterpret_cast<float4*>(CS + (size_t)dst * a.hd);
+      cp[0] = ca;
+      if (hq > 1) cp[1] = cb;
+      if (hq > 2) cp[2] = cc;
+      if (hq > 3) cp[3] = cd;
+      IND[dst] = ind;
+      if ((unsigned)ind < (unsigned)cap) PR[ind] += 1;           // prune[:, ind] += 1 (:572): one owner per original index
+    }
+    __syncthreads();                         // the wave totals are rewritten by the next chunk
+  }
+  for (int j = kept + tid; j < cnt; j += 256) IND[j] = -1;
+  if (tid == 0) a.cnt[s] = kept;
+}
+
+static int lg_prune_check(const LgPruneArgs& a) {
+  if ((a.D != 32 && a.D != 64) || a.hd < 4 || a.hd > 16 || (a.hd & 3)) return -1808;      // 16-byte row granules
+  if (a.B < 1 || a.M < 1 || a.N < 1 || !a.x || !a.cs || !a.cnt || !a.ind0 || !a.ind1 || !a.prune0 || !a.prune1) return -1808;
+  return 0;
+}
+
+int launch_lg_prune_init(const LgPruneArgs& a, const int32_t* n0, const int32_t* n1, hipStream_t s) {
+  if (int e = lg_prune_check(a)) return e;
+  hipLaunchKernelGGL(lg_prune_init_kernel, dim3(2 * a.B), dim3(256), 0, s, a, n0, n1);
+  return (int)hipGetLastError();
+}
+
+int launch_lg_prune(const LgPruneArgs& a, hipStream_t s) {
+  if (int e = lg_prune_check(a)) return e;
+  if (!a.w) return -1808;
+  if (a.D == 32) hipLaunchKernelGGL(lg_prune_kernel<32>, dim3(2 * a.B), dim3(256), 0, s, a);
+  else hipLaunchKernelGGL(lg_prune_kernel<64>, dim3(2 * a.B), dim3(256), 0, s, a);
+  return (int)hipGetLastError();
 }
 
 int launch_lg_assign(const LgAssignArgs& a, hipStream_t s) {

@@ -2,9 +2,19 @@
 
 Same constructor (``LightGlue(conf, weights_path=None)``), same ``state_dict`` keys and shapes, same ``forward(data)``
 contract (``required_data_keys`` + ``view0/view1["image_size"]``) and the same prediction dict; the arithmetic runs in
-``libkp2d_hip.so`` through include/kp2d_lightglue.h — the modules below only hold parameters.  Not built: training
-(loss, checkpointing), early stopping (``depth_confidence``) and point pruning (``width_confidence``) — the reference
-configs leave both at -1 — ``add_scale_ori`` and ``flash`` / mixed precision (the kernels are exact fp32).
+``libkp2d_hip.so`` through include/kp2d_lightglue.h — the modules below only hold parameters.
+
+Point pruning (``width_confidence > 0``, reference :535-545, :564-579, :585-597, :618-625) runs on the device
+(kp2d_lg_forward_pruned).  Deviations from the reference, all of them because a replayed HIP graph needs static shapes
+and no host round trip: the prediction keeps the PADDED shapes — ``log_assignment [B, M+1, N+1]`` and
+``ref_descriptors*`` hold the survivors in the leading rows / columns (survivor order), ``keep0 / keep1`` name their
+original indices and ``num_kept0 / num_kept1`` count them; ``matches*`` / ``matching_scores*`` / ``prune*`` are in the
+original index space as in the reference (``prune*`` int64).  ``unpad_pruned(pred, b)`` gives one pair's tensors in the
+reference's data-dependent shapes (it synchronises).  Every pair of a batch is pruned on its own (the reference
+asserts ``b == 1``), and a pair whose set becomes empty comes out unmatched instead of raising.
+
+Not built: training (loss, checkpointing), early stopping (``depth_confidence``; the reference cannot run it either),
+``add_scale_ori`` and ``flash`` / mixed precision (the kernels are exact fp32).
 """
 from __future__ import annotations
 
@@ -151,6 +161,8 @@ class LightGlue(nn.Module):
 
     def workspace_bytes(self, b, m, n, device):
         lib, h = self._engine(torch.device(device))
+        if self.conf.width_confidence > 0:
+            return int(lib.kp2d_lg_workspace_bytes_pruned(h, b, m, n))
         return int(lib.kp2d_lg_workspace_bytes(h, b, m, n))
 
     def _free(self):
@@ -185,8 +197,7 @@ class LightGlue(nn.Module):
             # (lightglue.py:624, :636), which this fork never defines (only the method confidence_threshold, :615)
             raise NotImplementedError("depth_confidence > 0 (early stopping) is not built; the reference raises "
                                       "AttributeError on it (confidence_thresholds is never defined)")
-        if self.conf.width_confidence > 0:
-            raise NotImplementedError("width_confidence > 0 (point pruning) is not built (reference configs leave it at -1)")
+        pruning = self.conf.width_confidence > 0          # do_point_pruning (:535; eval mode is checked above)
         kpts0, kpts1 = data["keypoints0"], data["keypoints1"]
         desc0, desc1 = data["descriptors0"].contiguous(), data["descriptors1"].contiguous()
         b, m, _ = kpts0.shape
@@ -227,7 +238,7 @@ class LightGlue(nn.Module):
         ms0, ms1 = torch.empty(b, m, device=dev), torch.empty(b, n, device=dev)
         ref = torch.empty(b * (m + n), d, device=dev)      # one buffer: the library copies both images' rows at once
         ref0, ref1 = ref[:b * m].view(b, m, d), ref[b * m:].view(b, n, d)
-        need = lib.kp2d_lg_workspace_bytes(h, b, m, n)
+        need = (lib.kp2d_lg_workspace_bytes_pruned if pruning else lib.kp2d_lg_workspace_bytes)(h, b, m, n)
         if self._ws_call is not None:
             if self._ws_call.numel() < need or self._ws_call.device != dev:
                 raise RuntimeError(f"using_workspace(): the buffer holds {self._ws_call.numel()} bytes, the forward needs {need}")
@@ -236,6 +247,24 @@ class LightGlue(nn.Module):
             if self._ws is None or self._ws.numel() < need or self._ws.device != dev:
                 self._ws = torch.empty(need, dtype=torch.uint8, device=dev)
             ws = self._ws
+        if pruning:
+            keep0 = torch.empty(b, m, dtype=torch.int32, device=dev)
+            keep1 = torch.empty(b, n, dtype=torch.int32, device=dev)
+            nk = torch.empty(2, b, dtype=torch.int32, device=dev)
+            pr0 = torch.empty(b, m, dtype=torch.int64, device=dev)
+            pr1 = torch.empty(b, n, dtype=torch.int64, device=dev)
+            _lib.check(lib.kp2d_lg_forward_pruned(
+                h, _ptr(kpts0), _ptr(kpts1), _ptr(desc0), _ptr(desc1), _ptr(size0), _ptr(size1), _ptr(cnt0), _ptr(cnt1),
+                b, m, n, float(self.conf.filter_threshold), float(self.conf.width_confidence), _ptr(scores),
+                _ptr(m0), _ptr(m1), _ptr(ms0), _ptr(ms1), _ptr(ref0), _ptr(ref1), _ptr(keep0), _ptr(keep1),
+                _ptr(nk[0]), _ptr(nk[1]), _ptr(pr0), _ptr(pr1), _ptr(ws), ws.numel(), _stream(dev)))
+            return {
+                "matches0": m0, "matches1": m1, "matching_scores0": ms0, "matching_scores1": ms1,
+                "ref_descriptors0": ref0[:, None], "ref_descriptors1": ref1[:, None],
+                "log_assignment": scores,
+                "prune0": pr0, "prune1": pr1,
+                "keep0": keep0, "keep1": keep1, "num_kept0": nk[0], "num_kept1": nk[1],
+            }
         _lib.check(lib.kp2d_lg_forward_counts(h, _ptr(kpts0), _ptr(kpts1), _ptr(desc0), _ptr(desc1), _ptr(size0), _ptr(size1),
                                               _ptr(cnt0), _ptr(cnt1), b, m, n, float(self.conf.filter_threshold), _ptr(scores),
                                               _ptr(m0), _ptr(m1), _ptr(ms0), _ptr(ms1), _ptr(ref0), _ptr(ref1),
@@ -248,6 +277,24 @@ class LightGlue(nn.Module):
             "log_assignment": scores,
             "prune0": prune[:b * m].view(b, m), "prune1": prune[b * m:].view(b, n),
         }
+
+
+def unpad_pruned(pred: dict, b: int = 0) -> dict:
+    """One pair of a pruned prediction in the reference's data-dependent shapes (lightglue.py:581-609 with b == 1):
+    ``log_assignment [1, m'+1, n'+1]`` (the survivors' block plus the dustbin row / column), ``ref_descriptors0/1
+    [1, 1, m' / n', D]``, ``ind0 / ind1`` (the survivors' original indices); matches, scores and prune are the pair's rows,
+    already in the original index space.  Deviation: reading ``num_kept*`` SYNCHRONISES with the device — the forward
+    itself never does."""
+    m, n = int(pred["num_kept0"][b]), int(pred["num_kept1"][b])
+    la = pred["log_assignment"][b]
+    rows = torch.cat([torch.arange(m, device=la.device), torch.tensor([la.shape[0] - 1], device=la.device)])
+    cols = torch.cat([torch.arange(n, device=la.device), torch.tensor([la.shape[1] - 1], device=la.device)])
+    out = {k: pred[k][b:b + 1] for k in ("matches0", "matches1", "matching_scores0", "matching_scores1", "prune0", "prune1")}
+    out["log_assignment"] = la[rows][:, cols][None]
+    out["ref_descriptors0"] = pred["ref_descriptors0"][b:b + 1, :, :m]
+    out["ref_descriptors1"] = pred["ref_descriptors1"][b:b + 1, :, :n]
+    out["ind0"], out["ind1"] = pred["keep0"][b:b + 1, :m].long(), pred["keep1"][b:b + 1, :n].long()
+    return out
 
 
 __main_model__ = LightGlue

@@ -6,6 +6,13 @@
 Prints one JSON line per pairs-per-step value: image pairs/s for extractor (both images) + K3 top-k + matcher, the matcher
 alone, and the `roofline` object of the step's dominant kernel family (HIP events around every launch of the extractor's
 forward on the 2 x pairs frames, as bench.py does; the matcher's ~25 launches are timed as a whole beside it).
+
+    python3 tools/bench_lightglue.py --width-confidence 0.6 [--parent-tree DIR] [--pairs 8] [--kpts 1024]
+
+Point pruning A/B of the matcher alone on seeded random keypoint sets: pairs/s with pruning off and on (three repeats each,
+same process, same box), the mean survivors per layer and set, and — with --parent-tree, a BUILT checkout of the parent
+commit — the parent's pairs/s with pruning off, three repeats in a fresh child process on the same inputs.  Written to
+profiles/lightglue_pruning.json.  Seeded random weights: the pruned share says nothing about trained weights.
 """
 import argparse
 import json
@@ -16,7 +23,10 @@ import time
 import numpy as np
 import torch
 
-sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+# --tree DIR: import the package from another (built) checkout, e.g. the parent commit, for an A/B on one box
+TREE = sys.argv[sys.argv.index("--tree") + 1] if "--tree" in sys.argv else ROOT
+sys.path.insert(0, TREE)
 
 
 def main():
@@ -31,10 +41,84 @@ def main():
     ap.add_argument("--filter-threshold", type=float, default=0.0,
                     help="LightGlue filter_threshold (seeded random weights give matching scores near 0: with the reference configs' "
                          "0.1 the filter and the compaction would see no match at all)")
+    ap.add_argument("--width-confidence", type=float, default=-1.0,
+                    help="> 0: the point-pruning A/B of the matcher alone -> profiles/lightglue_pruning.json")
+    ap.add_argument("--parent-tree", default="", help="built checkout of the parent commit: its pruning-off figure beside ours")
+    ap.add_argument("--tree", default="", help="import the package from this checkout instead of the tool's own")
+    ap.add_argument("--matcher-off-only", action="store_true", help="print the pruning-off repeats as one JSON line (child mode)")
+    ap.add_argument("--repeats", type=int, default=3)
     a = ap.parse_args()
+    if a.matcher_off_only:
+        print(json.dumps({"off_pairs_per_s": matcher_rates(a, -1.0)[0]}), flush=True)
+        return
+    if a.width_confidence > 0:
+        pruning_ab(a)
+        return
     for pairs in ([int(v) for v in a.sweep.split(",")] if a.sweep else [a.pairs]):
         a.pairs = pairs
         run(a)
+
+
+def matcher_rates(a, wc):
+    """([pairs/s] * repeats of the matcher alone, last prediction) on seeded random unit descriptors / keypoints."""
+    from lightglue.lightglue import LightGlue
+    from lightglue.lightglue_configs import get_light_glue_config
+    from nano_vs_slam_amd.synthetic import seeded_linear_state_dict
+    dev = torch.device("cuda:0")
+    conf = dict(get_light_glue_config("S"), filter_threshold=a.filter_threshold, width_confidence=wc)
+    lg = LightGlue(conf)
+    shapes = {k: tuple(v.shape) for k, v in lg.state_dict().items()}
+    lg.load_state_dict({k: torch.from_numpy(v) for k, v in seeded_linear_state_dict(shapes).items()})
+    lg = lg.to(dev).eval()
+    g = torch.Generator().manual_seed(0)
+    size = torch.tensor([[float(a.width), float(a.height)]]).expand(a.pairs, 2).contiguous().to(dev)
+    kp = lambda: (torch.rand(a.pairs, a.kpts, 2, generator=g) * torch.tensor([float(a.width), float(a.height)])).to(dev)
+    ds = lambda: torch.nn.functional.normalize(torch.randn(a.pairs, a.kpts, 32, generator=g), dim=-1).to(dev)
+    data = {"keypoints0": kp(), "keypoints1": kp(), "descriptors0": ds(), "descriptors1": ds(),
+            "view0": {"image_size": size}, "view1": {"image_size": size}}
+    rates, pred = [], None
+    with torch.no_grad():
+        for _ in range(a.repeats):
+            for _ in range(a.warmup):
+                pred = lg(data)
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            for _ in range(a.steps):
+                pred = lg(data)
+            torch.cuda.synchronize()
+            rates.append(round(a.pairs * a.steps / (time.perf_counter() - t0), 1))
+    return rates, pred
+
+
+def pruning_ab(a):
+    import subprocess
+    off, _ = matcher_rates(a, -1.0)
+    on, pred = matcher_rates(a, a.width_confidence)
+    n_layers = 4
+    # a point dropped after layer i holds i + 1, a survivor n_layers: survivors after layer i = #(prune > i + 1)
+    surv = {f"set{s}": [round(float((pred[f"prune{s}"] > i + 1).sum(1).float().mean()), 1) for i in range(n_layers - 1)]
+            for s in (0, 1)}
+    out = {"metric": "LightGlue S matcher alone, image pairs/s, point pruning off / on", "unit": "pairs/s",
+           "pairs_per_step": a.pairs, "keypoints": a.kpts, "steps": a.steps, "width_confidence": a.width_confidence,
+           "filter_threshold": a.filter_threshold, "off_pairs_per_s": off, "on_pairs_per_s": on,
+           "mean_survivors_after_layer": surv, "parent_off_pairs_per_s": None,
+           "data": "seeded random keypoints / unit descriptors, seeded random weights (the pruned share says nothing about "
+                   "trained weights)"}
+    if a.parent_tree:
+        # a fresh child process (its own HIP context and library), same inputs, pruning off
+        a.parent_tree = os.path.abspath(a.parent_tree)
+        cmd = [sys.executable, os.path.abspath(__file__), "--tree", a.parent_tree, "--matcher-off-only", "--pairs", str(a.pairs),
+               "--steps", str(a.steps), "--warmup", str(a.warmup), "--kpts", str(a.kpts), "--repeats", str(a.repeats),
+               "--filter-threshold", str(a.filter_threshold), "--height", str(a.height), "--width", str(a.width)]
+        r = subprocess.run(cmd, capture_output=True, text=True, cwd=a.parent_tree, timeout=600)
+        if r.returncode != 0:
+            raise RuntimeError(f"parent tree run failed ({r.returncode}): {r.stderr[-2000:]}")
+        out["parent_off_pairs_per_s"] = json.loads(r.stdout.strip().splitlines()[-1])["off_pairs_per_s"]
+    os.makedirs(os.path.join(ROOT, "profiles"), exist_ok=True)
+    with open(os.path.join(ROOT, "profiles", "lightglue_pruning.json"), "w") as f:
+        json.dump(out, f, indent=1)
+        f.write("\n")
+    print(json.dumps(out), flush=True)
 
 
 def run(a):
