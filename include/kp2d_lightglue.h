@@ -53,7 +53,16 @@ size_t kp2d_lg_workspace_bytes(const kp2d_lg* m, int B, int M, int N);
  * outputs (any of matches / scores / ref_desc may be NULL):
  *   log_assignment [B,M+1,N+1]   pred["log_assignment"]
  *   matches0 [B,M] / matches1 [B,N] int64 (-1: unmatched), mscores0 [B,M] / mscores1 [B,N]
- *   ref_desc0 [B,M,D] / ref_desc1 [B,N,D]  the last layer's descriptors (pred["ref_descriptors0/1"][:, 0]) */
+ *   ref_desc0 [B,M,D] / ref_desc1 [B,N,D]  the last layer's descriptors (pred["ref_descriptors0/1"][:, 0])
+ * Supported range.  The token-wise products and the attention run on split-fp16 operands (x = hi + lo, both fp16, fp32
+ * accumulation: 2^-22 relative, "fp32-grade"); the split does not saturate.  So every value that enters a product — the
+ * descriptors, every linear layer's output, the residual stream, q / k / v and the softmax weights — must stay below
+ * fp16's largest finite value, 65504, in magnitude: beyond it the hi half is inf and the outputs are inf / NaN (no
+ * error is reported).  Inside the range the results follow the float64 evaluation of the same network to a few fp32
+ * roundoffs at any descriptor scale: tests/test_gpu_lightglue_forms.py checks descriptors of norm 2^-16 .. 2^12 with
+ * unit-scale weights, where the largest intermediate value is 1.1e4 (LayerNorm bounds what the layers add, so the
+ * residual stream keeps the scale of the descriptors).  Operand components below fp16's subnormal step (2^-24) keep an
+ * ABSOLUTE precision of 2^-25, not a relative one.  Inputs must be finite. */
 int kp2d_lg_forward(kp2d_lg* m, const float* kpts0, const float* kpts1, const float* desc0, const float* desc1,
                     const float* size0, const float* size1, int B, int M, int N, float filter_threshold,
                     float* log_assignment, int64_t* matches0, int64_t* matches1, float* mscores0, float* mscores1,

@@ -8,6 +8,7 @@
 //                              written; K/V are walked in 64-key LDS chunks with an online softmax.
 //  * dwconv3x3_kernel          depthwise 3x3 + bias of MixFeedForward's DsConv2d (segformer.py:45-59)
 // The 1x1 convolutions (to_q, to_out, MixFFN) and the 2x2 stride-2 to_kv run through conv3x3.hip with taps = 1.
+#include "attention_form.h"
 #include "kp2d_kernels.h"
 #include "options.h"
 
@@ -659,32 +660,16 @@ __global__ __launch_bounds__(256, 4) void attention_ksplit_kernel(const AttnArgs
 }
 
 int launch_attention(const AttnArgs& a, hipStream_t s) {
-  const int d = a.C / a.heads;
-  if (a.C % a.heads || d > 64 || (d & 3) || (a.C & 3)) return -1402;
-  if (a.prec == 1 && d <= 16) {
-    // short sequences that leave most of the chip idle in the query-tiled kernel: split the keys over the waves
-    if ((long)((a.S + 127) / 128) * a.heads * a.B < tuning().att_ksplit && a.T >= 128) {
-      hipLaunchKernelGGL(attention_ksplit_kernel, dim3((a.S + 31) / 32, a.heads, a.B), dim3(256), 0, s, a);
-      return (int)hipGetLastError();
-    }
-    // 256 queries per workgroup halve the K / V staging per query (18 % of the kernel at 128); short sequences
-    // keep 128 so that the grid still covers the chip
-    const int big = tuning().att_q;
-    // (tiles * pairs, 1, 1): XCD-affine pair order (see the kernel); needs pairs % 8 == 0
-    const bool affine = (a.heads * a.B) % 8 == 0 && tuning().att_affine;
-    if (big == 256 && (long)((a.S + 255) / 256) * a.heads * a.B >= 512) {
-      const int tiles = (a.S + 255) / 256;
-      hipLaunchKernelGGL((attention_split_kernel<512, 6>), affine ? dim3(tiles * a.heads * a.B) : dim3(tiles, a.heads, a.B), dim3(512), 0, s, a);
-    } else {
-      const int tiles = (a.S + 127) / 128;
-      hipLaunchKernelGGL((attention_split_kernel<256, 4>), affine ? dim3(tiles * a.heads * a.B) : dim3(tiles, a.heads, a.B), dim3(256), 0, s, a);
-    }
-    return (int)hipGetLastError();
-  }
-  const dim3 grid((a.S + 63) / 64, a.heads, a.B);
-  if (d <= 16) hipLaunchKernelGGL(attention_kernel<1>, grid, dim3(256), 0, s, a);
-  else if (d <= 32) hipLaunchKernelGGL(attention_kernel<2>, grid, dim3(256), 0, s, a);
-  else hipLaunchKernelGGL(attention_kernel<4>, grid, dim3(256), 0, s, a);
+  AttForm f;
+  if (int e = choose_attention(a.S, a.T, a.heads, a.B, a.C, a.prec, tuning().att_ksplit, tuning().att_q, tuning().att_affine, f))
+    return e;
+  const dim3 grid(f.gx, f.gy, f.gz), block(f.block);
+  if (f.kernel == ATT_KSPLIT) hipLaunchKernelGGL(attention_ksplit_kernel, grid, block, 0, s, a);
+  else if (f.kernel == ATT_SPLIT && f.inst == 512) hipLaunchKernelGGL((attention_split_kernel<512, 6>), grid, block, 0, s, a);
+  else if (f.kernel == ATT_SPLIT) hipLaunchKernelGGL((attention_split_kernel<256, 4>), grid, block, 0, s, a);
+  else if (f.inst == 1) hipLaunchKernelGGL(attention_kernel<1>, grid, block, 0, s, a);
+  else if (f.inst == 2) hipLaunchKernelGGL(attention_kernel<2>, grid, block, 0, s, a);
+  else hipLaunchKernelGGL(attention_kernel<4>, grid, block, 0, s, a);
   return (int)hipGetLastError();
 }
 

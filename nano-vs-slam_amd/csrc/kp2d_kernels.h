@@ -164,6 +164,10 @@ struct LgTailArgs {
   const void* in = nullptr; const float* bn = nullptr;    // image [D -> nn] (nn = 64 or 96, padded), bias [nn]
   float* on = nullptr; int nn = 0, nos = 0, nvalid = 0;   // output, its row stride, columns stored
   const float* cs = nullptr; int hd = 0, rot_cols = 0;    // rotary: per-row cos | sin, head dim, leading columns that rotate
+  // optional: fp32 W^T [D][nn] of the next projection.  Its LAST stored column (nvalid - 1) is then an fp32 dot product
+  // instead of the split-fp16 one: the matchability logit, a sum that cancels and goes straight into log-sigmoid, where
+  // the split product's 2^-22 |w| |x| is an ABSOLUTE error of the log assignment (6e-5 at descriptors of norm 4096)
+  const float* wz = nullptr;
 };
 int launch_lg_tail(const LgTailArgs& a, hipStream_t s);
 

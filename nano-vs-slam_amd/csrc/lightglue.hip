@@ -18,6 +18,7 @@
 //  lg_prune_kernel      width_confidence > 0: matchability score, ordered compaction of the survivors (:564-579)
 #include "kp2d_kernels.h"
 #include "device_guard.h"
+#include "lightglue_form.h"
 #include "options.h"
 
 namespace kp2d {
@@ -286,7 +287,12 @@ __global__ __launch_bounds__(64 * NW) void lg_tail_mfma_kernel(const LgTailArgs 
     vec[e] = v;
   }
   // this lane's eight features of its row: 4 g .. 4 g + 3 and 16 + 4 g .. + 3 (the accumulator order)
-  float xv[8] = {}, cv[8] = {};
+  float xv[8] = {}, cv[8] = {}, wz[8] = {};
+  const int zc = a.wz ? a.nvalid - 1 : a.nvalid;             // the column computed in fp32 (LgTailArgs::wz); MFMA columns end here
+  if (a.wz) {
+#pragma unroll
+    for (int j = 0; j < 8; ++j) wz[j] = a.wz[(size_t)(4 * g + (j & 3) + 16 * (j >> 2)) * a.nn + zc];
+  }
   if (ok) {
     const float* xp = a.x + (size_t)row * 32 + 4 * g;
     *reinterpret_cast<float4*>(&xv[0]) = *reinterpret_cast<const float4*>(xp);
@@ -379,6 +385,14 @@ __global__ __launch_bounds__(64 * NW) void lg_tail_mfma_kernel(const LgTailArgs 
   }
   if (!a.nn) return;
   // ---- stage 4: the next projection of the updated rows, rotary on its leading columns ----
+  if (a.wz) {      // (uniform branch: every lane takes part in the two exchanges)
+    float z = 0.f;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) z = fmaf(xn[j], wz[j], z);
+    z += __shfl_xor(z, 16);
+    z += __shfl_xor(z, 32);
+    if (ok && g == 0) a.on[(size_t)row * a.nos + zc] = z + vec[256 + zc];
+  }
   lh8 nh, nl;
   lg_split8(xn, nh, nl);
   const int nt = a.nn >> 4;
@@ -397,12 +411,12 @@ __global__ __launch_bounds__(64 * NW) void lg_tail_mfma_kernel(const LgTailArgs 
     }
     if (!ok) continue;
     float* o = a.on + (size_t)row * a.nos + c;
-    if (c + 3 < a.nvalid) {
+    if (c + 3 < zc) {
       *reinterpret_cast<lf4*>(o) = y;
     } else {
 #pragma unroll
       for (int r = 0; r < 4; ++r)
-        if (c + r < a.nvalid) o[r] = y[r];
+        if (c + r < zc) o[r] = y[r];
     }
   }
 }
@@ -413,16 +427,17 @@ int launch_lg_tail(const LgTailArgs& a, hipStream_t s) {
   if (a.nn && (!a.in || !a.on || a.nvalid < 1 || a.nvalid > a.nn || (a.nos & 3) ||
                (a.cs && ((a.hd & 1) || 16 % a.hd || (a.rot_cols & 15)))))
     return -1805;
+  if (a.wz && (!a.nn || !a.bn)) return -1805;
   if (a.ctx && (!a.io || !a.i1 || !a.i2)) return -1807;
   if (!a.ctx && !a.nn) return -1807;
   // four waves per workgroup also at one image pair (2048 rows = 32 workgroups): one-wave workgroups spread wider but
   // each stages the 42 KB of operands with 64 lanes — 0.236 vs 0.204 ms per forward
-  const int nw = tuning().lg_tail_nw ? tuning().lg_tail_nw : 4;
+  const int nw = lg_tail_waves(tuning().lg_tail_nw);
+  if (!nw) return -1806;
   const size_t lds = (size_t)(LG_IMG_O + LG_IMG_1 + LG_IMG_2 + LG_IMG_N) * 2 + LG_TAIL_VEC * sizeof(float);
   const dim3 grid((a.rows + 16 * nw - 1) / (16 * nw));
   if (nw == 4) hipLaunchKernelGGL(lg_tail_mfma_kernel<4>, grid, dim3(256), lds, s, a);
-  else if (nw == 1) hipLaunchKernelGGL(lg_tail_mfma_kernel<1>, grid, dim3(64), lds, s, a);
-  else return -1806;
+  else hipLaunchKernelGGL(lg_tail_mfma_kernel<1>, grid, dim3(64), lds, s, a);
   return (int)hipGetLastError();
 }
 
@@ -612,7 +627,11 @@ __device__ __forceinline__ float log_sigmoid(float x) { return fminf(x, 0.f) - l
 // (sigmoid_log_double_softmax, :363-376); the tiles of the first tile column / row also write the border column / row
 // (logsigmoid(-z)); plus the tile's row / column max and argmax of the final values for filter_matches (:403-404)
 __global__ __launch_bounds__(256) void lg_finalize_kernel(const LgAssignArgs a) {
-  __shared__ float s_base[64], s_col[64], s_ls1[64];
+  // per row / column of the tile: maximum and log-sum of its log-softmax, and its log-sigmoid.  The maxima stay apart
+  // from the rest: sim - max is taken first, as log_softmax does (exact near the maximum).  One merged term per row,
+  // 2 sim + (ls0 - lse_row) - lse_col, cancels at the magnitude of sim and leaves its ulp: 1.5e-2 at |sim| = 1e5
+  // (descriptors of norm 256), where the separate form keeps the error relative to the result.
+  __shared__ float s_rmx[64], s_rlg[64], s_ls0[64], s_cmx[64], s_clg[64], s_ls1[64];
   __shared__ float s_cm[4][64];
   __shared__ int s_ci[4][64];
   __shared__ float tile[64 * LG_TP];
@@ -635,27 +654,27 @@ __global__ __launch_bounds__(256) void lg_finalize_kernel(const LgAssignArgs a) 
   }
   if (tid < 64) {
     const int i = i0 + tid;
-    float base = 0.f;
+    float mx = 0.f, lg = 0.f, ls0 = 0.f;
     if (i < M) {
       float m, s;
       lse_merge_partials(a.rp_m + (size_t)b * TN * M + i, a.rp_s + (size_t)b * TN * M + i, TN, M, m, s);
       const float z0 = z0p[(size_t)i * a.fs];
-      base = log_sigmoid(z0) - (m + logf(s));
+      mx = m; lg = logf(s); ls0 = log_sigmoid(z0);
       if (blockIdx.x == 0) sc[(size_t)i * (N + 1) + N] = log_sigmoid(-z0);
     }
-    s_base[tid] = base;
+    s_rmx[tid] = mx; s_rlg[tid] = lg; s_ls0[tid] = ls0;
   } else if (tid < 128) {
     const int c = tid - 64, j = j0 + c;
-    float cl = 0.f, ls1 = 0.f;
+    float mx = 0.f, lg = 0.f, ls1 = 0.f;
     if (j < N) {
       float m, s;
       lse_merge_partials(a.cp_m + (size_t)b * TM * N + j, a.cp_s + (size_t)b * TM * N + j, TM, N, m, s);
-      cl = m + logf(s);
+      mx = m; lg = logf(s);
       const float z1 = z1p[(size_t)j * a.fs];
       ls1 = log_sigmoid(z1);
       if (blockIdx.y == 0) sc[(size_t)M * (N + 1) + j] = log_sigmoid(-z1);
     }
-    s_col[c] = cl; s_ls1[c] = ls1;
+    s_cmx[c] = mx; s_clg[c] = lg; s_ls1[c] = ls1;
   } else if (tid == 128 && blockIdx.x == 0 && blockIdx.y == 0) {
     sc[(size_t)M * (N + 1) + N] = 0.f;
   }
@@ -667,7 +686,7 @@ __global__ __launch_bounds__(256) void lg_finalize_kernel(const LgAssignArgs a) 
 #pragma unroll
   for (int r = 0; r < 4; ++r) {
     const int i = i0 + 4 * ty + r;
-    const float base = s_base[4 * ty + r];
+    const float rmx = s_rmx[4 * ty + r], rlg = s_rlg[4 * ty + r], ls0 = s_ls0[4 * ty + r];
 #pragma unroll
     for (int c = 0; c < 4; ++c) {
       const int j = j0 + 4 * tx + c;
@@ -675,7 +694,9 @@ __global__ __launch_bounds__(256) void lg_finalize_kernel(const LgAssignArgs a) 
       if (i < M && j < N) {
         float* p = &tile[(4 * ty + r) * LG_TP + 4 * tx + c];
         // (a padding row / column: -inf — no assignment mass, never a maximum)
-        if (i < Mv && j < Nv) x = 2.f * *p + base - s_col[4 * tx + c] + s_ls1[4 * tx + c];
+        // log_softmax over the row + log_softmax over the column + the certainties (:363-376), each as the reference forms it
+        if (i < Mv && j < Nv)
+          x = (((*p - rmx) - rlg) + ((*p - s_cmx[4 * tx + c]) - s_clg[4 * tx + c])) + (ls0 + s_ls1[4 * tx + c]);
         *p = x;
       }
       v[r][c] = x;

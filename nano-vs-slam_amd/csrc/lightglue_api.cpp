@@ -13,6 +13,7 @@
 #include "api_common.h"
 #include "device_guard.h"
 #include "kp2d_kernels.h"
+#include "lightglue_form.h"
 #include "options.h"
 
 using namespace kp2d;
@@ -292,12 +293,12 @@ int run_forward(kp2d_lg* m, const float* kpts0, const float* kpts1, const float*
     LG_CHECK(launch_lg_linear(a, st), what);
     return KP2D_OK;
   };
-  // D = 32 (configs S, A): out_proj / to_out + ffn + residual as ONE row-local kernel (lightglue.hip lg_tail_kernel)
-  const bool fuse_tail = tuning().lg_fuse;
+  // D = 32 (configs S, A): out_proj / to_out + ffn + residual as ONE row-local kernel (lightglue.hip lg_tail_kernel).
   // `next`: the token-wise projection that follows the block (the cross block's [to_qk | to_v], the next layer's Wqkv
   // with rotary, the final projection) runs in the tail's launch on the rows it has just updated: 8 launches fewer
   // per forward than one lg_linear per projection (the matcher is a chain of ~35 dependent launches of ~10 us)
-  const bool fuse_next = tuning().lg_fuse_next;
+  const LgForm form = choose_lg_form(d, tuning().lg_fuse, tuning().lg_fuse_next);      // (lightglue_form.h)
+  const bool fuse_tail = form.fuse_tail, fused = form.fused;
   auto tail = [&](const Lin& proj, const Ffn& f, const char* what, const Lin* next, float* nout, int nos, int nvalid,
                   bool rotary) -> int {
     LgTailArgs t{};
@@ -306,12 +307,23 @@ int run_forward(kp2d_lg* m, const float* kpts0, const float* kpts1, const float*
     if (next) {
       t.in = blob + next->mf; t.bn = blob + next->b; t.on = nout; t.nn = next->nout; t.nos = nos; t.nvalid = nvalid;
       if (rotary) { t.cs = CS; t.hd = hd; t.rot_cols = 2 * d; }
+      if (next == &m->final) t.wz = blob + next->w;      // the matchability logit (column d) as an fp32 dot product
     }
     LG_CHECK(launch_lg_tail(t, st), what);
     return KP2D_OK;
   };
-  const bool fused = fuse_tail && fuse_next && d == 32;
-  const float scale = 1.f / std::sqrt((float)hd);
+  // the sequences of one attention launch (lightglue_form.h): q / k rows of T3 with `cols` columns, keys counted by CNT
+  auto attention = [&](const LgAttLaunch& l, int cols, int k_off, int v_off, const char* what) -> int {
+    const size_t rq = l.q_set ? (size_t)R0 : 0, rk = l.k_set ? (size_t)R0 : 0;
+    AttnArgs t{T3 + rq * cols, T3 + rk * cols, CTX + rq * d, l.B, l.S, l.T, d, heads, 1.f / std::sqrt((float)hd)};
+    t.q_stride = cols; t.kv_stride = cols; t.k_off = k_off; t.v_off = v_off; t.out_stride = d;
+    t.prec = 1;      // split-fp16 MFMA (fp32-grade, attention.hip): 3x faster than the fp32 16x16x4 kernel at head dim 8
+    t.kv_bshift = l.kv_bshift;
+    t.tcount = CNT ? CNT + (l.k_set ? B : 0) : nullptr;      // the counts of the set the KEYS come from
+    LG_CHECK(launch_attention(t, st), what);
+    return KP2D_OK;
+  };
+  LgAttLaunch att[2];
   for (int i = 0; i < m->cfg.n_layers; ++i) {
     const Layer& L = m->layers[i];
     // ---- SelfBlock (lightglue.py:247-261), both images in one launch per token-wise layer ----
@@ -328,21 +340,10 @@ int run_forward(kp2d_lg* m, const float* kpts0, const float* kpts1, const float*
       } else if (!fused) {             // (fused, i > 0: done by the previous tail)
         LG_CHECK(launch_lg_linear(a, st), "self_attn.Wqkv");
       }
-      if (M == N) {   // both images as one batch of 2B sequences
-        AttnArgs t{T3, T3, CTX, 2 * B, M, M, d, heads, scale};
-        t.q_stride = 3 * d; t.kv_stride = 3 * d; t.k_off = d; t.v_off = 2 * d; t.out_stride = d; t.prec = 1;
-        t.tcount = CNT;
-        LG_CHECK(launch_attention(t, st), "self_attn.inner_attn");
-      } else {
-        for (int set = 0; set < 2; ++set) {
-          const size_t r0 = set ? (size_t)R0 : 0;
-          const int n = set ? N : M;
-          AttnArgs t{T3 + r0 * 3 * d, T3 + r0 * 3 * d, CTX + r0 * d, B, n, n, d, heads, scale};
-          t.q_stride = 3 * d; t.kv_stride = 3 * d; t.k_off = d; t.v_off = 2 * d; t.out_stride = d;
-          t.prec = 1;      // split-fp16 MFMA (fp32-grade, attention.hip): 3x faster than the fp32 16x16x4 kernel at head dim 8
-          t.tcount = CNT ? CNT + (set ? B : 0) : nullptr;
-          LG_CHECK(launch_attention(t, st), "self_attn.inner_attn");
-        }
+      // rows of T3: [q | k | v].  M == N: both images as one batch of 2B sequences
+      for (int j = 0, n = lg_attention_launches(B, M, N, false, att); j < n; ++j) {
+        int rc = attention(att[j], 3 * d, d, 2 * d, "self_attn.inner_attn");
+        if (rc != KP2D_OK) return rc;
       }
       if (fuse_tail && d == 32) {
         int rc = tail(L.out_proj, L.fs, "self_attn tail", fused ? &L.qkv_x : nullptr, T3, 2 * d, 2 * d, false);
@@ -358,21 +359,11 @@ int run_forward(kp2d_lg* m, const float* kpts0, const float* kpts1, const float*
     {
       LgLinArgs a = linear(L.qkv_x, X, d, d, nullptr, 0, 0, T3, 2 * d, R, 2 * d, LG_EPI_NONE);
       if (!fused) LG_CHECK(launch_lg_linear(a, st), "cross_attn.to_qk/to_v");
-      if (M == N) {   // both directions in one launch: sequence b attends to sequence (b + B) mod 2B
-        AttnArgs t{T3, T3, CTX, 2 * B, M, M, d, heads, scale};
-        t.q_stride = 2 * d; t.kv_stride = 2 * d; t.k_off = 0; t.v_off = d; t.out_stride = d; t.prec = 1;
-        t.kv_bshift = B;
-        t.tcount = CNT;
-        LG_CHECK(launch_attention(t, st), "cross_attn");
-      } else {
-        for (int set = 0; set < 2; ++set) {
-          const size_t rq = set ? (size_t)R0 : 0, rk = set ? 0 : (size_t)R0;
-          AttnArgs t{T3 + rq * 2 * d, T3 + rk * 2 * d, CTX + rq * d, B, set ? N : M, set ? M : N, d, heads, scale};
-          t.q_stride = 2 * d; t.kv_stride = 2 * d; t.k_off = 0; t.v_off = d; t.out_stride = d;
-          t.prec = 1;
-          t.tcount = CNT ? CNT + (set ? 0 : B) : nullptr;      // the keys are the OTHER set's rows
-          LG_CHECK(launch_attention(t, st), "cross_attn");
-        }
+      // rows of T3: [qk | v], the keys are the OTHER set's rows.  M == N: both directions in one launch, sequence b
+      // attends to sequence (b + B) mod 2B
+      for (int j = 0, n = lg_attention_launches(B, M, N, true, att); j < n; ++j) {
+        int rc = attention(att[j], 2 * d, 0, d, "cross_attn");
+        if (rc != KP2D_OK) return rc;
       }
       if (fuse_tail && d == 32) {
         const bool last = i + 1 == m->cfg.n_layers;
