@@ -440,6 +440,70 @@ int kp2d_kmeans_train(const float* x, int64_t n, int dim, float* centroids /* in
                       uint32_t flags, uint64_t seed, float* obj /* [niter] */, int64_t* assign, float* dist,
                       int64_t* counts, void* scratch, size_t scratch_bytes, void* stream);
 
+/* ---- Fine-tuning the NetVLAD layer: forward with saved state, triplet loss, backward, Adam (nano-vs-slam_amd/csrc/vlad_train.hip) ----
+ * The gradient step of the reference's place-recognition training (train_visloc.py:249-282: NetVLAD forward,
+ * TripletMarginLoss(margin ** 0.5, p=2, reduction="sum") / nNeg, backward, Adam) for the two parameters of the layer,
+ * conv.weight W [K,C] and centroids cent [K,C].  Everything upstream of the layer is frozen and no gradient with respect
+ * to x is formed.  Stateless like the calls above: caller-owned device buffers, the caller's stream, no synchronisation,
+ * no host round trip; arguments are checked on the host before any launch.
+ *   Shapes: x [N,C,S] fp32 PLANAR (a frame's C channel planes of S pixels: only_encoder's [N,C,Hc,Wc]); 1 <= N <= 65535,
+ *     S >= 1 (else KP2D_ERR_ARG); K % 4 == 0, C % 4 == 0, 4 <= K <= 64, K * C <= 8192 (the forward's limits) and
+ *     (2 K (C + 1) + 64 (C + 1) + 64 (K + 1)) * 4 <= 160 KB of LDS (else KP2D_ERR_UNSUPPORTED); K = 64, C = 128 takes 115 712 B.
+ *   scratch: kp2d_vlad_train_scratch_bytes(N, S, C, K) bytes (0: bad shape), 16-byte aligned, shared by the three calls of a
+ *     step; a shorter one is KP2D_ERR_ARG.  kp2d_triplet_loss needs 4 (B + n_neg) bytes and takes them
+ *     at the head of the scratch it is given; in a step's shared scratch that head is free between the forward and the backward
+ *     (the forward has read its tile partials there, the backward writes them all again before it reads one).
+ *
+ * kp2d_vlad_forward_train: per frame
+ *       xh[s] = x[:,s] / max(||x[:,s]||, 1e-12);  a = softmax_k(xh W^T);  r[k] = sum_s a[s,k]
+ *       U[k] = sum_s a[s,k] xh[s] - r[k] cent[k];  n[k] = max(||U[k]||, 1e-12);  V[k] = U[k] / n[k]
+ *       g = max(||V||_F, 1e-12);  v = V / g
+ *   -> vlad [N, K*C] (v flattened k-major: the model's own "vlad" output in fp32 arithmetic) and saved [N, K*C + 2K + 4]:
+ *   per frame V [K*C], n [K], r [K], g, three zeros.  saved is what kp2d_vlad_backward reads; nothing of size [S,K] is kept.
+ *
+ * kp2d_triplet_loss: vlad [N, dim] with rows [q_0..q_{B-1}, p_0..p_{B-1}, the n_neg negatives in query order], N = 2B + n_neg,
+ *   B >= 1, n_neg >= 0; neg_offset [B + 1] int32 on the device, the exclusive prefix of the queries' negative counts
+ *   (neg_offset[0] = 0, neg_offset[B] = n_neg); margin >= 0 is the SQUARED margin, the hinge uses margin ** 0.5.
+ *       d(u, w) = || u - w + 1e-6 ||_2          (torch's pairwise_distance: eps added to the difference)
+ *       loss = (1 / n_neg) sum_i sum_j max(0, d(q_i, p_i) - d(q_i, n_ij) + margin ** 0.5)
+ *   -> loss (one float), dvlad [N, dim] = d loss / d vlad, n_active (one int32: triplets with a positive hinge).
+ *   Differences and the eps are fp32 operations; a distance's squares, their sum and its square root are float64 and the
+ *   distance is then rounded to fp32; every hinge term and every gradient entry is fp32 arithmetic on those distances; the
+ *   hinge terms are added in float64 and the loss is rounded to fp32 once.
+ *   Each row's gradient is gathered from its own triplets in triplet order: dq_i and dp_i are sums over j, a negative's
+ *   row has one term; the rows of a query without negatives, of an inactive negative and of a positive without an active
+ *   triplet are exactly zero.  n_neg == 0: loss = 0, dvlad = 0, n_active = 0.  The kernels clamp every offset to [0, n_neg],
+ *   so a wrong prefix reads and writes nothing outside vlad / dvlad; its result is then unspecified.
+ *
+ * kp2d_vlad_backward: x, W, cent as in the forward, saved from it, dvlad [N, K*C] -> d_weight [K,C], d_centroids [K,C]:
+ *       dV = (dv - v <v,dv>) / g;  dU[k] = (dV[k] - V[k] <V[k],dV[k]>) / n[k];  dcent[k] = -r[k] dU[k]
+ *       da[s,k] = <xh[s],dU[k]> - <cent[k],dU[k]>;  dz[s,k] = a[s,k] (da[s,k] - sum_j a[s,j] da[s,j]);  dW[k] = sum_s dz[s,k] xh[s]
+ *   summed over a frame's pixels, then over the frames.  a is recomputed per 64-pixel tile; pixels past S are masked in
+ *   both [S,K] products and in the softmax.  (Where a norm met its 1e-12 floor the formulas above are used as they stand.)
+ *
+ * kp2d_adam_step: torch.optim.Adam's update (no weight decay, no amsgrad) of n floats, step = 1, 2, ...:
+ *       m = m + (1 - beta1) (grad - m);  v = beta2 v + (1 - beta2) grad^2
+ *       denom = sqrt(v) / sqrt(1 - beta2^step) + eps;  param -= lr / (1 - beta1^step) * m / denom
+ *   The two bias corrections are formed on the host in double.  lr >= 0, 0 <= beta < 1, eps >= 0 (else KP2D_ERR_ARG).
+ *   A zero gradient on zero moments leaves param bit-unchanged.
+ *
+ *   Arithmetic: exact fp32 on the vector ALU (no split-fp16 anywhere in training), float64 where stated.
+ *   Determinism: no float atomics.  Tile t of a frame covers pixels [64 t, 64 t + 64); a tile's sums run over its pixels
+ *     in pixel order, a frame's tiles are added in tile order and the frames in frame order, one workgroup per tile
+ *     whatever N is: a frame's sums depend on S alone, the order over frames on N alone.  All outputs are bit-identical from
+ *     run to run, vlad / saved rows do not depend on the other frames of the call, and frames behind the others whose
+ *     dvlad rows are zero change no bit of d_weight or d_centroids. */
+size_t kp2d_vlad_train_scratch_bytes(int N, int S, int C, int K);
+int kp2d_vlad_forward_train(const float* x, const float* weight, const float* centroids, int N, int S, int C, int K,
+                            float* vlad, float* saved, void* scratch, size_t scratch_bytes, void* stream);
+int kp2d_triplet_loss(const float* vlad, int B, const int32_t* neg_offset, int n_neg, int dim, double margin, float* loss,
+                      float* dvlad, int32_t* n_active, void* scratch, size_t scratch_bytes, void* stream);
+int kp2d_vlad_backward(const float* x, const float* weight, const float* centroids, const float* saved, const float* dvlad,
+                       int N, int S, int C, int K, float* d_weight, float* d_centroids, void* scratch, size_t scratch_bytes,
+                       void* stream);
+int kp2d_adam_step(float* param, const float* grad, float* m, float* v, int64_t n, int64_t step, double lr, double beta1,
+                   double beta2, double eps, void* stream);
+
 /* ---- Scores of the dense heads: segmentation counts and depth sums (nano-vs-slam_amd/csrc/dense_metrics.hip) -----
  * Replace what the reference's evaluate_segmentation takes from segmentation_models_pytorch (smp.metrics.get_stats,
  * src/evaluation/segmentation.py:42-48) and the reductions inside its compute_errors_torch
