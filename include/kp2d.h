@@ -504,6 +504,61 @@ int kp2d_vlad_backward(const float* x, const float* weight, const float* centroi
 int kp2d_adam_step(float* param, const float* grad, float* m, float* v, int64_t n, int64_t step, double lr, double beta1,
                    double beta2, double eps, void* stream);
 
+/* ---- Fine-tuning the whole place-recognition head: Conv + BatchNorm + (Leaky)ReLU forward and backward, and NetVLAD's
+ *      input gradient (nano-vs-slam_amd/csrc/vpr_head_train.hip, vlad_train.hip) ----
+ * What the reference's train_visloc.py --freeze_backbone moves: vlad_head.convlad{1,2,3}.conv.weight, .bn.weight, .bn.bias and
+ * the two NetVLAD parameters above, all updated by kp2d_adam_step.  The backbone and every other head are frozen.
+ * Stated deviation: BatchNorm runs on its RUNNING statistics, which are not updated, and Dropout2d is off, where the
+ * reference puts the head in model.train(): this is vlad_head.eval() under autograd.  Loss, row order, the squared margin and
+ * the Adam conventions are those of kp2d_triplet_loss and kp2d_adam_step.  Stateless like the calls above: caller-owned
+ * device buffers, the caller's stream, no synchronisation, no host round trip; arguments are checked on the host before any
+ * launch.
+ *   Shapes: tensors are fp32 PLANAR [N, C, H, W]; w is [Cout, Cin, 3, 3].  1 <= N <= 65535, H, W >= 1 (else KP2D_ERR_ARG);
+ *     Cin % 16 == 0, Cout % 16 == 0, 16 <= Cin, Cout <= 128, H * W <= 2^30 (else KP2D_ERR_UNSUPPORTED).
+ *   scratch: kp2d_cbr_train_scratch_bytes(N, H, W, Cin, Cout) bytes (0: bad shape), 16-byte aligned; a shorter one is
+ *     KP2D_ERR_ARG.  Each call writes what it reads there, so one buffer of the largest layer's size serves every layer.
+ *   slope: 0.01 for LeakyReLU, 0 for ReLU; 0 <= slope < 1 (else KP2D_ERR_ARG).
+ *
+ * kp2d_cbr_forward_train: c = conv3x3(x, w) (stride 1, padding 1, no bias);  y = act(scale c + shift) per output channel,
+ *       act(v) = v > 0 ? v : slope v;  scale = gamma / sqrt(var + eps), shift = beta - mean scale (formed by the caller)
+ *   -> y [N, Cout, H, W] and c [N, Cout, H, W], the convolution's own result, which kp2d_cbr_backward reads.
+ *
+ * kp2d_cbr_backward: x, w, scale as in the forward, mean and invstd = 1 / sqrt(var + eps) [Cout], y and c from the forward,
+ *   dy [N, Cout, H, W]:
+ *       dpre = dy (y > 0 ? 1 : slope)        (torch's rule; y > 0 is the pre-activation's sign for both slopes)
+ *       d_beta[co] = sum dpre;  d_gamma[co] = sum dpre (c - mean) invstd      (from c itself: right where gamma = 0)
+ *       dc = dpre scale
+ *       d_weight[co,ci,ky,kx] = sum_{n,y,x} dc[n,co,y,x] x[n,ci,y+ky-1,x+kx-1]
+ *       dx[n,ci,y,x] = sum_{co,ky,kx} dc[n,co,y-ky+1,x-kx+1] w[co,ci,ky,kx]      (skipped when dx is NULL: the first layer
+ *                                                                                  behind a frozen backbone)
+ *   -> d_weight [Cout, Cin, 3, 3], d_gamma [Cout], d_beta [Cout], dx [N, Cin, H, W].  d_weight, d_gamma and d_beta have the
+ *   same bits with and without dx.
+ *
+ * kp2d_vlad_backward_input: the gradient kp2d_vlad_backward does not form.  Arguments and scratch as kp2d_vlad_backward
+ *   (kp2d_vlad_train_scratch_bytes); additionally C <= 128, and for K > C one more [64][K + 1] of LDS (else
+ *   KP2D_ERR_UNSUPPORTED; for K <= C the tile takes kp2d_vlad_backward's LDS).  With dU, a and dz as kp2d_vlad_backward
+ *   forms them per 64-pixel tile:
+ *       dxh[s] = sum_k a[s,k] dU[k] + sum_k dz[s,k] W[k];  dx[:,s] = (dxh[s] - xh[s] <xh[s], dxh[s]>) / max(||x[:,s]||, 1e-12)
+ *   -> dx [N, C, S].  It recomputes dU and the tile's softmax: it shares nothing in memory with kp2d_vlad_backward,
+ *   whose results it leaves as they were.  A frame whose dvlad row is zero gets dx = 0 exactly.
+ *
+ *   Arithmetic: exact fp32 everywhere (no split-fp16).  The three convolution-shaped products are implicit GEMMs on
+ *     v_mfma_f32_16x16x4_f32, bit for bit an fp32 fma chain; everything else runs on the vector ALU.
+ *   Determinism: no float atomics.  An output tile is 8 x 16 pixels; the weight gradient is cut over the tiles (frame-major)
+ *     into at most 128 slabs, a slab's sum runs over its tiles and pixels in order, the slabs are added in slab order, the
+ *     BatchNorm sums per frame in a fixed order and then in frame order: the order depends on (N, H, W) alone, every output
+ *     is bit-identical from run to run, and a frame whose dy is zero everywhere changes no bit of any gradient whatever its
+ *     x, y and c hold. */
+size_t kp2d_cbr_train_scratch_bytes(int N, int H, int W, int Cin, int Cout);
+int kp2d_cbr_forward_train(const float* x, const float* w, const float* scale, const float* shift, double slope, int N, int H,
+                           int W, int Cin, int Cout, float* y, float* c, void* scratch, size_t scratch_bytes, void* stream);
+int kp2d_cbr_backward(const float* x, const float* w, const float* scale, const float* mean, const float* invstd, double slope,
+                      const float* y, const float* c, const float* dy, int N, int H, int W, int Cin, int Cout, float* d_weight,
+                      float* d_gamma, float* d_beta, float* dx /* may be NULL */, void* scratch, size_t scratch_bytes,
+                      void* stream);
+int kp2d_vlad_backward_input(const float* x, const float* weight, const float* centroids, const float* saved, const float* dvlad,
+                             int N, int S, int C, int K, float* dx, void* scratch, size_t scratch_bytes, void* stream);
+
 /* ---- Scores of the dense heads: segmentation counts and depth sums (nano-vs-slam_amd/csrc/dense_metrics.hip) -----
  * Replace what the reference's evaluate_segmentation takes from segmentation_models_pytorch (smp.metrics.get_stats,
  * src/evaluation/segmentation.py:42-48) and the reductions inside its compute_errors_torch

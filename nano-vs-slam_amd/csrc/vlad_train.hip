@@ -18,6 +18,8 @@
 //   vt_tile_kernel<true>    grid (tiles, N): the forward's tile again (a is recomputed, no [S, K] tensor is stored), the
 //                           second [S, K] product with dU in the same loop as the logits, dz in place of a, the tile's
 //                           [K, C] sum of dz xh -> one partial per (frame, tile)
+//   vt_tile_kernel<true, true>   the same tile for kp2d_vlad_backward_input: a is kept beside dz, and the tile writes
+//                           dx = the channel normalisation's backward of a dU + dz W instead of a dW partial
 //   vt_frame_sum_kernel     grid (ceil(K C / 256), N): a frame's tile partials added in tile order
 //   vt_grad_sum_kernel      grid (ceil(K C / 256)): the frames' sums added in frame order -> dW, dcent
 //   tl_dist_kernel / tl_grad_kernel   the triplet loss: one workgroup per pair distance (squares summed in float64, stored
@@ -34,6 +36,7 @@
 
 #include "api_common.h"
 #include "device_guard.h"
+#include "train_common.h"
 
 using namespace kp2d;
 
@@ -51,25 +54,16 @@ constexpr size_t tile_lds_floats(int K, int C, bool bwd) {
 // backward (2 * 64 * 129 + 64 * 129 + 64 * 65) * 4 = 115 712 B of the 160 KB a workgroup may take.
 static_assert(tile_lds_floats(64, 128, false) * 4 == 82688, "forward tile LDS");
 static_assert(tile_lds_floats(64, 128, true) * 4 == 115712 && tile_lds_floats(64, 128, true) * 4 <= LDS_BUDGET, "backward tile LDS");
+// The input-gradient form (kp2d_vlad_backward_input) keeps a beside dz.  K <= C: in the rows of xh, whose entries each thread
+// has taken into registers by then (the backward's own LDS, so as many workgroups share a CU as there: the second one halves
+// the time at K = C = 64); K > C: one more [64][K + 1].
+constexpr int DX_MAX_C = 128;     // a thread holds its C / 4 <= 32 entries of xh and of dxh in registers
+constexpr size_t tile_lds_floats_dx(int K, int C) { return tile_lds_floats(K, C, true) + (K <= C ? 0 : (size_t)VT * (K + 1)); }
+static_assert(tile_lds_floats_dx(64, 128) * 4 == 115712 && tile_lds_floats_dx(64, 16) * 4 == 46336,"input-gradient tile LDS");
 
 __host__ __device__ inline int tiles_of(int S) { return (S + VT - 1) / VT; }
 // floats of a frame's saved record: V [K C], n [K], r [K], g and three floats of padding (rows stay 16-byte aligned)
 __host__ __device__ inline size_t saved_stride(int K, int C) { return (size_t)K * C + 2 * (size_t)K + 4; }
-
-// sum of n floats p[0], p[stride], ... in index order; eight loads in flight, the additions strictly sequential
-__device__ __forceinline__ float ordered_sum(const float* p, size_t stride, int n) {
-  float acc = 0.f;
-  int i = 0;
-  for (; i + 8 <= n; i += 8) {
-    float t[8];
-#pragma unroll
-    for (int j = 0; j < 8; ++j) t[j] = p[(size_t)(i + j) * stride];
-#pragma unroll
-    for (int j = 0; j < 8; ++j) acc += t[j];
-  }
-  for (; i < n; ++i) acc += p[(size_t)i * stride];
-  return acc;
-}
 
 struct TileArgs {
   const float* x;      // [N][C][S] planar
@@ -77,11 +71,15 @@ struct TileArgs {
   const float* du;     // BWD: [N][K][C]
   const float* cdu;    // BWD: [N][K]  <cent[k], dU[k]>
   float* part;         // [N][tiles][K C + K] (forward) / [N][tiles][K C] (backward)
+  float* dx;           // DX: [N][C][S] planar
   int S, C, K;
 };
 
-template <bool BWD>
+// DX (with BWD): the gradient with respect to x in place of the tile's dW partial:
+//   dxh[s] = sum_k a[s,k] dU[k] + sum_k dz[s,k] W[k];  dx[:,s] = (dxh[s] - xh[s] <xh[s], dxh[s]>) / max(||x[:,s]||, 1e-12)
+template <bool BWD, bool DX = false>
 __global__ __launch_bounds__(256) void vt_tile_kernel(const TileArgs a) {
+  static_assert(BWD || !DX, "the input gradient is a backward form");
   extern __shared__ __attribute__((aligned(16))) float sm[];
   const int C = a.C, K = a.K, S = a.S;
   const int CP = C + 1, KP = K + 1, KC = K * C;
@@ -89,6 +87,10 @@ __global__ __launch_bounds__(256) void vt_tile_kernel(const TileArgs a) {
   float* s_d = s_w + K * CP;                         // BWD: [K][CP]
   float* s_x = s_d + (BWD ? K * CP : 0);             // [VT][CP]
   float* s_a = s_x + VT * CP;                        // [VT][KP]
+  // DX: a beside dz, [VT][A2P].  K <= C: in the rows of xh (a pixel's row is read by its own four threads alone, lanes of one
+  // wave, which take their entries into registers before they write a there); K > C: behind s_a
+  float* s_a2 = (K <= C) ? s_x : s_a + VT * KP;
+  const int A2P = (K <= C) ? CP : KP;
   const int tid = threadIdx.x;
   const int tile = blockIdx.x, b = blockIdx.y;
   const int t0 = tile * VT;
@@ -108,6 +110,8 @@ __global__ __launch_bounds__(256) void vt_tile_kernel(const TileArgs a) {
   __syncthreads();
   const int p = tid >> 2, q = tid & 3;               // 4 threads per pixel
   const int cq = C >> 2, kq = K >> 2;
+  float xinv = 0.f;                                  // DX: 1 / max(||x[:,p]||, 1e-12)
+  float xo[DX ? DX_MAX_C / 4 : 1];                   // DX: this thread's C / 4 entries of xh[p]
   {  // descriptor-wise L2 normalisation (F.normalize, eps 1e-12)
     float ss = 0.f;
     for (int c = q * cq; c < (q + 1) * cq; ++c) { const float v = s_x[p * CP + c]; ss = fmaf(v, v, ss); }
@@ -115,6 +119,7 @@ __global__ __launch_bounds__(256) void vt_tile_kernel(const TileArgs a) {
     ss += __shfl_xor(ss, 2);
     const float inv = 1.f / fmaxf(sqrtf(ss), 1e-12f);
     for (int c = q * cq; c < (q + 1) * cq; ++c) s_x[p * CP + c] *= inv;
+    if (DX) xinv = inv;
   }
   __syncthreads();
   {  // this thread owns clusters [q kq, (q + 1) kq) of pixel p: logits (and <xh, dU[k]>) in one walk over the channels
@@ -158,11 +163,45 @@ __global__ __launch_bounds__(256) void vt_tile_kernel(const TileArgs a) {
       inner += __shfl_xor(inner, 1);
       inner += __shfl_xor(inner, 2);
     }
+    if (DX) {
+#pragma unroll
+      for (int cc = 0; cc < DX_MAX_C / 4; ++cc) xo[cc] = (cc < cq) ? s_x[p * CP + q * cq + cc] : 0.f;
+    }
 #pragma unroll
     for (int j = 0; j < 16; ++j)
-      if (j < kq) s_a[p * KP + q * kq + j] = BWD ? lg[j] * (da[j] - inner) : lg[j];
+      if (j < kq) {
+        s_a[p * KP + q * kq + j] = BWD ? lg[j] * (da[j] - inner) : lg[j];
+        if (DX) s_a2[p * A2P + q * kq + j] = lg[j];
+      }
   }
   __syncthreads();
+  if (DX) {  // this thread's C / 4 channels of pixel p: both [S, K] x [K, C] products, then the normalisation's backward
+    float dxh[DX_MAX_C / 4];
+#pragma unroll
+    for (int cc = 0; cc < DX_MAX_C / 4; ++cc) dxh[cc] = 0.f;
+    const int c0 = q * cq;
+    for (int k = 0; k < K; ++k) {
+      const float ak = s_a2[p * A2P + k], zk = s_a[p * KP + k];
+      const float* dr = &s_d[k * CP + c0];
+      const float* wr = &s_w[k * CP + c0];
+#pragma unroll
+      for (int cc = 0; cc < DX_MAX_C / 4; ++cc)
+        if (cc < cq) dxh[cc] = fmaf(zk, wr[cc], fmaf(ak, dr[cc], dxh[cc]));
+    }
+    float dot = 0.f;
+#pragma unroll
+    for (int cc = 0; cc < DX_MAX_C / 4; ++cc)
+      if (cc < cq) dot = fmaf(xo[cc], dxh[cc], dot);
+    dot += __shfl_xor(dot, 1);
+    dot += __shfl_xor(dot, 2);
+    if (p < np) {
+      float* o = a.dx + (size_t)b * C * S + t0 + p;
+#pragma unroll
+      for (int cc = 0; cc < DX_MAX_C / 4; ++cc)
+        if (cc < cq) o[(size_t)(c0 + cc) * S] = (dxh[cc] - xo[cc] * dot) * xinv;
+    }
+    return;
+  }
   // the tile's [K][C] sum over its 64 pixels, pixel 0 first
   float* dst = a.part + ((size_t)b * gridDim.x + tile) * (BWD ? KC : KC + K);
   for (int e = tid; e < KC; e += 256) {
@@ -458,13 +497,13 @@ const char* shape_problem(int N, int S, int C, int K, int* code) {
   return nullptr;
 }
 
-template <bool BWD>
+template <bool BWD, bool DX = false>
 int launch_tile(const TileArgs& a, int N, hipStream_t st) {
-  const size_t lds = tile_lds_floats(a.K, a.C, BWD) * sizeof(float);
+  const size_t lds = (DX ? tile_lds_floats_dx(a.K, a.C) : tile_lds_floats(a.K, a.C, BWD)) * sizeof(float);
   const dim3 grid(tiles_of(a.S), N);
   static PerDeviceOnce once;      // per device: the tensors may live on any visible device
-  if (int e = lds_opt_in(once, reinterpret_cast<const void*>(&vt_tile_kernel<BWD>))) return e;
-  hipLaunchKernelGGL((vt_tile_kernel<BWD>), grid, dim3(256), lds, st, a);
+  if (int e = lds_opt_in(once, reinterpret_cast<const void*>(&vt_tile_kernel<BWD, DX>))) return e;
+  hipLaunchKernelGGL((vt_tile_kernel<BWD, DX>), grid, dim3(256), lds, st, a);
   return (int)hipGetLastError();
 }
 
@@ -527,6 +566,30 @@ int kp2d_vlad_backward(const float* x, const float* weight, const float* centroi
   HIP_TRY(hipGetLastError());
   hipLaunchKernelGGL(vt_grad_sum_kernel, dim3((KC + 255) / 256), dim3(256), 0, st, p.fs, p.dcf, d_weight, d_centroids, N, KC);
   HIP_TRY(hipGetLastError());
+  return KP2D_OK;
+}
+
+int kp2d_vlad_backward_input(const float* x, const float* weight, const float* centroids, const float* saved, const float* dvlad,
+                             int N, int S, int C, int K, float* dx, void* scratch, size_t scratch_bytes, void* stream) {
+  int code;
+  if (const char* why = shape_problem(N, S, C, K, &code)) return fail(code, "vlad_backward_input: %s (N %d, S %d, C %d, K %d)", why, N, S, C, K);
+  if (C > DX_MAX_C || tile_lds_floats_dx(K, C) * sizeof(float) > (size_t)LDS_BUDGET)
+    return fail(KP2D_ERR_UNSUPPORTED, "vlad_backward_input: needs C <= %d and a tile within 160 KB of LDS (C %d, K %d)", DX_MAX_C, C, K);
+  if (!x || !weight || !centroids || !saved || !dvlad || !dx || !scratch) return fail(KP2D_ERR_ARG, "null argument");
+  if (misaligned(x, 4) || misaligned(weight, 4) || misaligned(centroids, 4) || misaligned(saved, 4) || misaligned(dvlad, 4) ||
+      misaligned(dx, 4) || misaligned(scratch, 16))
+    return fail(KP2D_ERR_ARG, "vlad_backward_input: float arrays must be 4-byte aligned, scratch 16-byte");
+  const TrainPlan p = train_plan(scratch, N, S, C, K);
+  if (scratch_bytes < p.total) return fail(KP2D_ERR_ARG, "vlad_backward_input scratch %zu B < required %zu B (kp2d_vlad_train_scratch_bytes)", scratch_bytes, p.total);
+  hipStream_t st = (hipStream_t)stream;
+  DeviceGuard guard(x, st);
+  DuArgs d{};      // dU and <cent[k], dU[k]> as kp2d_vlad_backward forms them (the frame's dcent lands in scratch, unused)
+  d.saved = saved; d.dv = dvlad; d.cent = centroids; d.du = p.du; d.cdu = p.cdu; d.dcf = p.dcf; d.C = C; d.K = K;
+  hipLaunchKernelGGL(vt_du_kernel, dim3(N), dim3(256), (size_t)(K * C + 4) * sizeof(float), st, d);
+  HIP_TRY(hipGetLastError());
+  TileArgs t{};
+  t.x = x; t.w = weight; t.du = p.du; t.cdu = p.cdu; t.dx = dx; t.S = S; t.C = C; t.K = K;
+  if (int e = launch_tile<true, true>(t, N, st)) return fail(KP2D_ERR_HIP, "vlad_backward_input: tile kernel: %d", e);
   return KP2D_OK;
 }
 

@@ -714,6 +714,23 @@ class _KP2DTinyBase(nn.Module):
                                         _ptr(enc), None, _ptr(ws), ws.numel(), _stream(x.device)))
         return enc
 
+    def backbone_features(self, x):
+        """The backbone's output map [B, c4, Hc, Wc] that ``vlad_head.convlad1`` reads, in the engine's current precision:
+        the tap on ``backbone.conv4b`` (kp2d_set_tap) of an only-encoder forward, which runs the backbone and the VPR
+        encoder and no other head.  What ``vpr_head_training.VPRHeadTrainer.step_features`` takes: the backbone is
+        frozen there, so the map is computed once."""
+        if x.dim() != 4 or x.shape[0] < 1:
+            raise ValueError(f"expected float32 [B >= 1, ., H, W] input, got {x.dtype} {tuple(x.shape)}")
+        B, _, H, W = x.shape
+        eng = self._get_engine(x.device)
+        tap = torch.full((B, int(self.channel_dims[3]), H // self.cell, W // self.cell), float("nan"), device=x.device)
+        _lib.check(eng.lib.kp2d_set_tap(eng.handle, b"backbone.conv4b", _ptr(tap), tap.numel()))
+        try:
+            self.only_encoder(x)
+        finally:
+            _lib.check(eng.lib.kp2d_set_tap(eng.handle, None, None, 0))
+        return tap
+
 
 def _common_init(self, *, nfeatures, device, channel_dims, bn_momentum, nClasses, num_clusters, downsample,
                  use_attention, mem_efficient, upscale_method, remove_netvlad, leaky_relu, depth, encoder_dim,
