@@ -508,8 +508,8 @@ int kp2d_adam_step(float* param, const float* grad, float* m, float* v, int64_t 
  *      input gradient (nano-vs-slam_amd/csrc/vpr_head_train.hip, vlad_train.hip) ----
  * What the reference's train_visloc.py --freeze_backbone moves: vlad_head.convlad{1,2,3}.conv.weight, .bn.weight, .bn.bias and
  * the two NetVLAD parameters above, all updated by kp2d_adam_step.  The backbone and every other head are frozen.
- * Stated deviation: BatchNorm runs on its RUNNING statistics, which are not updated, and Dropout2d is off, where the
- * reference puts the head in model.train(): this is vlad_head.eval() under autograd.  Loss, row order, the squared margin and
+ * These three calls run BatchNorm on its RUNNING statistics, which are not updated, without Dropout2d: vlad_head.eval() under
+ * autograd.  The reference's own mode, the head under model.train(), is the next section's.  Loss, row order, the squared margin and
  * the Adam conventions are those of kp2d_triplet_loss and kp2d_adam_step.  Stateless like the calls above: caller-owned
  * device buffers, the caller's stream, no synchronisation, no host round trip; arguments are checked on the host before any
  * launch.
@@ -558,6 +558,51 @@ int kp2d_cbr_backward(const float* x, const float* w, const float* scale, const 
                       void* stream);
 int kp2d_vlad_backward_input(const float* x, const float* weight, const float* centroids, const float* saved, const float* dvlad,
                              int N, int S, int C, int K, float* dx, void* scratch, size_t scratch_bytes, void* stream);
+
+/* ---- The same layers as the reference's model.train() runs them: BatchNorm on the batch's own statistics, Dropout2d
+ *      (nano-vs-slam_amd/csrc/vpr_head_train.hip) ----
+ * train_visloc.py calls model.train() before its loop, so convlad1..3 normalise with the batch's mean and variance, move
+ * their running statistics, and Dropout2d(0.2) zeroes whole channels of convlad1's output.  Shapes, slope, scratch
+ * (kp2d_cbr_train_scratch_bytes; the per-frame partials take the area of the backward's BatchNorm sums), alignment, null and
+ * stream rules are those of kp2d_cbr_forward_train / kp2d_cbr_backward above; everything is refused before the first launch.
+ * M = N H W is the number of values per channel; M < 2 is KP2D_ERR_ARG in both calls (torch raises there too).
+ *
+ * kp2d_cbr_forward_batchnorm: gamma, beta [Cout]; drop [N, Cout] holding 0 or 1 / (1 - p), or NULL: no dropout;
+ *   running_mean, running_var [Cout], updated in place, or NULL: not tracked; eps >= 0, 0 <= momentum <= 1 (else KP2D_ERR_ARG).
+ *       c = conv3x3(x, w);  mean = sum c / M;  var = sum (c - mean)^2 / M  (BIASED);  invstd = 1 / sqrt(var + eps)
+ *       y = act(gamma invstd (c - mean) + beta) drop[n, co]
+ *       running_mean = (1 - m) running_mean + m mean;  running_var = (1 - m) running_var + m var M / (M - 1)  (UNBIASED)
+ *   -> y, c [N, Cout, H, W], mean, invstd [Cout] (what kp2d_cbr_backward_batchnorm reads).  1 - m, m and m M / (M - 1) are
+ *   formed on the host in double and rounded to fp32 once.  The variance is never formed as E[c^2] - mean^2: each (frame,
+ *   channel) plane gives its mean and its sum of squared distances from that mean (two passes over the plane), and the planes,
+ *   all of H W values, are merged by Chan's formula: mean = (sum_b mean_b) / N, M var = sum_b M2_b + H W sum_b (mean_b - mean)^2.
+ *
+ * kp2d_cbr_backward_batchnorm: mean, invstd, y, c from the forward, the same drop; per pixel, with xhat = (c - mean) invstd:
+ *       g = dy drop[n, co] (y > 0 ? 1 : slope);  d_beta = sum g;  d_gamma = sum g xhat  (from c: right where gamma = 0)
+ *       dc = gamma invstd (g - d_beta / M - xhat d_gamma / M)
+ *   and d_weight, dx from dc as in kp2d_cbr_backward (dx may be NULL; d_weight, d_gamma, d_beta have the same bits either way).
+ *   A dropped plane (drop = 0) has y = 0 and g = 0 exactly; its dc is not zero: the plane is part of the statistics.
+ *
+ * kp2d_dropout2d_mask: drop[n, c] = u >= p ? 1 / (1 - p) : 0, 0 <= p < 1 (else KP2D_ERR_ARG), N, C >= 1, N C < 2^31,
+ *   0 <= step < 2^32, layer >= 0.  The draw is counter-based (mix = splitmix64's finaliser, nano-vs-slam_amd/csrc/mix64.h), all
+ *   arithmetic modulo 2^64:
+ *       h = mix(mix(mix(seed + 0x9E3779B97F4A7C15) ^ (step << 32 | layer)) ^ (n << 32 | c));  u = (h >> 11) 2^-53  (in double)
+ *   It is this library's stream, not torch's: the stated deviation of kp2d_kmeans_* and kp2d_vpr_mine.  1 / (1 - p) is
+ *   formed in double and rounded to fp32.
+ *
+ *   Determinism: no float atomics.  A plane's sums run over a thread's strided elements in order, then the wave's 64 lanes,
+ *     then the four waves; the planes' partials are added in frame order; the order depends on (N, H, W) alone and every
+ *     output is bit-identical from run to run.  Every frame enters mean and var, so here a frame whose dy is zero does change
+ *     the other frames' gradients: that property belongs to the running-statistics calls alone. */
+int kp2d_cbr_forward_batchnorm(const float* x, const float* w, const float* gamma, const float* beta, double eps, double slope,
+                               const float* drop /* may be NULL */, double momentum, float* running_mean /* may be NULL */,
+                               float* running_var /* may be NULL */, int N, int H, int W, int Cin, int Cout, float* y, float* c,
+                               float* mean, float* invstd, void* scratch, size_t scratch_bytes, void* stream);
+int kp2d_cbr_backward_batchnorm(const float* x, const float* w, const float* gamma, const float* mean, const float* invstd,
+                                double slope, const float* drop /* may be NULL */, const float* y, const float* c, const float* dy,
+                                int N, int H, int W, int Cin, int Cout, float* d_weight, float* d_gamma, float* d_beta,
+                                float* dx /* may be NULL */, void* scratch, size_t scratch_bytes, void* stream);
+int kp2d_dropout2d_mask(float* drop, int N, int C, double p, uint64_t seed, int64_t step, int layer, void* stream);
 
 /* ---- Scores of the dense heads: segmentation counts and depth sums (nano-vs-slam_amd/csrc/dense_metrics.hip) -----
  * Replace what the reference's evaluate_segmentation takes from segmentation_models_pytorch (smp.metrics.get_stats,

@@ -132,6 +132,10 @@ SIGNATURES = {
     "kp2d_cbr_forward_train": (C.c_int, [_P] * 4 + [C.c_double] + [C.c_int] * 5 + [_P, _P, _P, C.c_size_t, _P]),
     "kp2d_cbr_backward": (C.c_int, [_P] * 5 + [C.c_double] + [_P] * 3 + [C.c_int] * 5 + [_P] * 4 + [_P, C.c_size_t, _P]),
     "kp2d_vlad_backward_input": (C.c_int, [_P] * 5 + [C.c_int] * 4 + [_P, _P, C.c_size_t, _P]),
+    "kp2d_cbr_forward_batchnorm": (C.c_int, [_P] * 4 + [C.c_double, C.c_double, _P, C.c_double, _P, _P] + [C.c_int] * 5 + [_P] * 4 +
+                                   [_P, C.c_size_t, _P]),
+    "kp2d_cbr_backward_batchnorm": (C.c_int, [_P] * 5 + [C.c_double] + [_P] * 4 + [C.c_int] * 5 + [_P] * 4 + [_P, C.c_size_t, _P]),
+    "kp2d_dropout2d_mask": (C.c_int, [_P, C.c_int, C.c_int, C.c_double, C.c_uint64, C.c_int64, C.c_int, _P]),
     "kp2d_seg_conf_lds_max": (C.c_int, []),
     "kp2d_seg_stats": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int64, C.c_int, C.c_int64, _P, _P, _P, _P, _P]),
     "kp2d_depth_scratch_bytes": (C.c_size_t, [C.c_int, C.c_int64]),

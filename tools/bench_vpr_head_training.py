@@ -2,6 +2,7 @@
 
     python3 tools/bench_vpr_head_training.py [--B 4] [--negs 10] [--H 120] [--W 160] [--config S]
                                              [--out profiles/vpr_head_training.json] [--commit NAME] [--baseline-only]
+                                             [--bn batch] [--dropout 0.2]
 
 Inputs: the reference's training defaults (train_visloc.py: batch of 4 queries, 10 negatives each, 120 x 160 frames, margin
 0.1, lr 1e-4) on synthetic frames; the backbone map comes from model.backbone_features once (model.forward_with_tap where
@@ -14,6 +15,11 @@ softmax, one einsum, both normalisations) + torch autograd + torch.nn.TripletMar
 reduction="sum") / nNeg on gathered rows + torch.optim.Adam over the eleven parameters, on the same device.  The baseline
 needs nothing of this package's training modules (--baseline-only), so it runs on earlier commits too.
 HIP-event time per step over a window of back-to-back steps after a warm-up, three repeats; all three are recorded.
+--bn batch [--dropout P] times the reference's own mode, the head under model.train(): VPRHeadTrainer(bn="batch", dropout=P)
+against the restated head with F.batch_norm(training=True) on the batch's statistics, its running-statistics update, and
+F.dropout2d(P) behind convlad1; the two sides draw different masks, so their first losses are compared only at P = 0.  The
+default --out is then profiles/vpr_head_training_batchnorm.json.  --merge-into FILE writes the result under --label in an
+existing JSON file instead of a file of its own (several modes and commits side by side in one file).
 Nothing is gated on the result; the file is where the numbers go.
 """
 from __future__ import annotations
@@ -55,8 +61,15 @@ def main():
     ap.add_argument("--steps", type=int, default=50)
     ap.add_argument("--commit", default="", help="recorded when the tree is not a git checkout")
     ap.add_argument("--baseline-only", action="store_true")
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "vpr_head_training.json"))
+    ap.add_argument("--bn", choices=("running", "batch"), default="running")
+    ap.add_argument("--dropout", type=float, default=0.0)
+    ap.add_argument("--out", default=None)
+    ap.add_argument("--merge-into", default=None, help="an existing JSON file: the result goes under --label there")
+    ap.add_argument("--label", default=None)
     args = ap.parse_args()
+    batch = args.bn == "batch"
+    if args.out is None:
+        args.out = os.path.join(ROOT, "profiles", "vpr_head_training_batchnorm.json" if batch or args.dropout else "vpr_head_training.json")
     import numpy as np
     import torch
     import torch.nn.functional as F
@@ -86,7 +99,7 @@ def main():
     slope = 0.01 if model.leaky_relu else 0.0
     res = {"device": torch.cuda.get_device_name(0), "config": args.config, "B": B, "negatives_per_query": args.negs, "frames": N,
            "H": args.H, "W": args.W, "map": [int(feat.shape[2]), int(feat.shape[3])], "Cin": c4, "K": int(K), "C": int(C), "margin": 0.1,
-           "lr": 1e-4, "steps_per_window": args.steps,
+           "lr": 1e-4, "steps_per_window": args.steps, "bn": args.bn, "dropout": args.dropout,
            "commit": subprocess.run(["git", "describe", "--always", "--dirty"], cwd=ROOT, capture_output=True,
                                     text=True).stdout.strip() or args.commit or "unknown"}
 
@@ -94,7 +107,7 @@ def main():
     convs = [torch.nn.Parameter(l.conv.weight.detach().clone()) for l in layers]
     gammas = [torch.nn.Parameter(l.bn.weight.detach().clone()) for l in layers]
     betas = [torch.nn.Parameter(l.bn.bias.detach().clone()) for l in layers]
-    stats = [(l.bn.running_mean.detach().clone(), l.bn.running_var.detach().clone(), l.bn.eps) for l in layers]
+    stats = [(l.bn.running_mean.detach().clone(), l.bn.running_var.detach().clone(), l.bn.eps, l.bn.momentum) for l in layers]
     w = torch.nn.Parameter(head.netvlad.conv.weight.detach().clone().view(K, C))
     cent = torch.nn.Parameter(head.netvlad.centroids.detach().clone())
     opt = torch.optim.Adam([t for trio in zip(convs, gammas, betas) for t in trio] + [w, cent], lr=1e-4)
@@ -102,9 +115,11 @@ def main():
     owner = torch.repeat_interleave(torch.arange(B, device=dev), torch.tensor(counts, device=dev))
 
     def torch_head(x):
-        for cw, g, b, (mean, var, eps) in zip(convs, gammas, betas, stats):
-            x = F.batch_norm(F.conv2d(x, cw, padding=1), mean, var, g, b, training=False, eps=eps)
+        for i, (cw, g, b, (mean, var, eps, mom)) in enumerate(zip(convs, gammas, betas, stats)):
+            x = F.batch_norm(F.conv2d(x, cw, padding=1), mean, var, g, b, training=batch, momentum=mom, eps=eps)
             x = F.leaky_relu(x, slope) if slope else F.relu(x)
+            if i == 0 and args.dropout:
+                x = F.dropout2d(x, args.dropout, training=True)
         xh = F.normalize(x.view(N, C, -1), p=2.0, dim=1)
         a = F.softmax(torch.einsum("kc,ncs->nks", w, xh), dim=1)
         vlad = torch.einsum("nks,ncs->nkc", a, xh) - a.sum(-1).unsqueeze(2) * cent.unsqueeze(0)
@@ -125,12 +140,14 @@ def main():
 
     if not args.baseline_only:
         from nano_vs_slam_amd import vlad_training as vt, vpr_head_training as ht
-        trainer = ht.VPRHeadTrainer(model, lr=1e-4, margin=0.1)
+        kw = {"bn": args.bn, "dropout": args.dropout} if batch or args.dropout else {}      # (earlier commits: no such arguments)
+        trainer = ht.VPRHeadTrainer(model, lr=1e-4, margin=0.1, **kw)
         cnt_dev = torch.tensor(counts, dtype=torch.int32, device=dev)
         first = float(trainer.step_features(feat, B, cnt_dev))
         ms = timed(lambda: trainer.step_features(feat, B, cnt_dev), args.steps)
         res.update(step_features_ms=ms, step_features_ms_best=min(ms), first_loss=first)
-        assert abs(first - res["torch_first_loss"]) < 1e-5, (first, res["torch_first_loss"])
+        if not args.dropout:
+            assert abs(first - res["torch_first_loss"]) < 1e-5, (first, res["torch_first_loss"])
 
         # one step's calls, each on its own
         split = {}
@@ -147,12 +164,23 @@ def main():
             split[name] = s.elapsed_time(e) / reps
             return out
 
+        drop = None
+        if args.dropout:
+            drop = one("dropout2d_scale", lambda: ht.dropout2d_scale(N, int(C), args.dropout, 0, 1, 1, dev))
         acts, x = [], feat
         for i, layer in enumerate(layers):
-            vec = ht.bn_vectors(layer.bn)
-            y, c = one(f"convlad{i + 1}_forward", lambda: ht.cbr_forward(x, layer.conv.weight, vec[0], vec[1], slope))
-            acts.append((x, y, c, vec))
-            x = y
+            d = drop if i == 0 else None
+            if batch:
+                bn = layer.bn
+                y, c, mean, invstd = one(f"convlad{i + 1}_forward", lambda: ht.cbr_forward_batch(
+                    x, layer.conv.weight, bn.weight, bn.bias, bn.eps, slope, d, (bn.running_mean, bn.running_var), bn.momentum))
+                acts.append((x, y, c, (None, None, mean, invstd)))
+                x = y
+            else:
+                vec = ht.bn_vectors(layer.bn)
+                y, c = one(f"convlad{i + 1}_forward", lambda: ht.cbr_forward(x, layer.conv.weight, vec[0], vec[1], slope))
+                acts.append((x, y, c, vec))
+                x = y if d is None else y * d[:, :, None, None]
         nw, nc = head.netvlad.conv.weight, head.netvlad.centroids
         vlad, saved = one("netvlad_forward", lambda: vt.netvlad_forward(x, nw, nc))
         loss, dvlad, _ = one("triplet_loss", lambda: vt.triplet_margin_loss(vlad, B, cnt_dev, 0.1))
@@ -161,15 +189,27 @@ def main():
         for i in (2, 1, 0):
             lx, ly, lc, (scale, _, mean, invstd) = acts[i]
             g = dy
-            out = one(f"convlad{i + 1}_backward" + ("" if i else "_no_dx"),
-                      lambda: ht.cbr_backward(lx, layers[i].conv.weight, scale, mean, invstd, ly, lc, g, slope, need_dx=i > 0))
+            d = drop if i == 0 else None
+            name = f"convlad{i + 1}_backward" + ("" if i else "_no_dx")
+            if batch:
+                out = one(name, lambda: ht.cbr_backward_batch(lx, layers[i].conv.weight, layers[i].bn.weight, mean, invstd, ly, lc, g,
+                                                              slope, d, need_dx=i > 0))
+            else:
+                if d is not None:
+                    g = g * d[:, :, None, None]
+                out = one(name, lambda: ht.cbr_backward(lx, layers[i].conv.weight, scale, mean, invstd, ly, lc, g, slope, need_dx=i > 0))
             dy = out[3]
         p = torch.zeros_like(out[0]).view(-1)
         m, v = torch.zeros_like(p), torch.zeros_like(p)
         one("adam_conv_weight", lambda: vt.adam_step(p, out[0].view(-1), m, v, 1))
         res["split_ms"] = split
 
-    os.makedirs(os.path.dirname(args.out), exist_ok=True)
+    if args.merge_into:
+        args.out = args.merge_into
+        whole = json.load(open(args.out)) if os.path.exists(args.out) else {}
+        whole[args.label or f"{args.bn}_dropout_{args.dropout}_{res['commit']}"] = res
+        res = whole
+    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
     with open(args.out, "w") as f:
         json.dump(res, f, indent=1)
         f.write("\n")
