@@ -671,6 +671,75 @@ size_t kp2d_depth_scratch_bytes(int B, int64_t n);
 int kp2d_depth_sums(const float* gt, const float* pred, const uint8_t* valid, int B, int64_t n, double min_depth,
                     double max_depth, double* sums, void* scratch, size_t scratch_bytes, void* stream);
 
+/* ---- Fine-tuning the segmentation head: the last layer, the dense loss, pooling and pixel shuffle
+ *      (nano-vs-slam_amd/csrc/seg_train.hip; declared here because it uses KP2D_SEG_* above) ----
+ * What the reference's train_multitask.py moves in its V2 SegmentationHead (modules/decoders/segmentation.py:8-157) under
+ * _compute_segmentation_loss (KeypointNetwithIOLoss.py:880-884), next to the Conv + BatchNorm + (Leaky)ReLU layers of
+ * kp2d_cbr_forward_train / kp2d_cbr_backward and kp2d_adam_step, which it reuses as they are.  The head runs as
+ * seg_head.eval() under autograd: BatchNorm on its running statistics, no Dropout2d.  Stateless like those calls: caller-owned
+ * device buffers, the caller's stream, no synchronisation, no host round trip; every argument is checked on the host before
+ * the first launch.  Tensors are fp32 PLANAR [N, C, H, W]; 1 <= N <= 65535 and every extent >= 1 (else KP2D_ERR_ARG).
+ *
+ * kp2d_conv_bias_forward_train: y = conv3x3(x, w) (stride 1, padding 1) + bias, w [Cout, Cin, 3, 3], bias [Cout].
+ *   Cin % 16 == 0, 16 <= Cin <= 128, 1 <= Cout <= 128 (ANY count, not only multiples of 16), H * W <= 2^30 (else
+ *   KP2D_ERR_UNSUPPORTED).  scratch: kp2d_conv_bias_scratch_bytes(N, H, W, Cin, Cout) bytes (0: bad shape), 16-byte aligned.
+ * kp2d_conv_bias_backward: dy [N, Cout, H, W] ->
+ *       d_bias[co] = sum_{n,y,x} dy[n,co,y,x]      (a plane's sum, then the frames in frame order)
+ *       d_weight[co,ci,ky,kx] = sum_{n,y,x} dy[n,co,y,x] x[n,ci,y+ky-1,x+kx-1]
+ *       dx[n,ci,y,x] = sum_{co,ky,kx} dy[n,co,y-ky+1,x-kx+1] w[co,ci,ky,kx]      (skipped when dx is NULL)
+ *   d_weight and d_bias have the same bits with and without dx.  The three products are the implicit GEMMs of
+ *   kp2d_cbr_* on v_mfma_f32_16x16x4_f32 with Cout padded to the next multiple of 16 in the packed weights (which the call
+ *   writes in full, zeros included, whatever scratch held): a padded channel reads no memory, contributes exact zeros and
+ *   is never stored.  Tiles, slabs and their order are those of kp2d_cbr_backward.
+ *
+ * kp2d_seg_loss: logits [N, C, HW], labels [N, HW] of label_dtype KP2D_SEG_U8 / _I32 / _I64, 1 <= C <= 128, HW <= 2^30,
+ *   ignore_index: any int64, KP2D_SEG_NO_IGNORE: ignore nothing; ce_weight, dice_weight finite and >= 0.
+ *       loss = ce_weight CE + dice_weight Dice          (the reference: 0.5 and 1.5)
+ *   A pixel whose label equals ignore_index is IGNORED; a pixel that is not ignored and whose label lies outside [0, C) is
+ *   STRAY: it is treated as ignored and counted in *stray (valid data has none).  Every other pixel is VALID (*valid).
+ *   With p = softmax(z) over the classes and t the one-hot label, both taken as 0 at pixels that are not valid:
+ *       CE = (1 / valid) sum_valid -log p[label]                     torch.nn.CrossEntropyLoss(ignore_index), mean reduction
+ *       I_c = sum p_c t_c;  S_c = sum (p_c + t_c)  (over the whole batch);  score_c = 2 I_c / max(S_c, 1e-7)
+ *       Dice = (1 / C) sum_c [sum t_c > 0] (1 - score_c)
+ *   A class absent from the labels adds 0 to the sum and stays in the divisor C.  Dice is smp.losses.DiceLoss(
+ *   mode="multiclass", ignore_index=...) with smooth = 0, eps = 1e-7 as the reference constructs it, RESTATED from smp's
+ *   definition: segmentation_models_pytorch was not available to run against, so it is not pinned; CE is pinned to torch.
+ *   -> *loss, dlogits [N, C, HW] = d loss / d logits, *valid, *stray (int64).  Per valid pixel, with
+ *   g_c = d Dice / d p_c = [present_c] (-2 t_c / (C S_c) + 2 I_c / (C S_c^2)):
+ *       dlogits_j = (ce_weight / valid) (p_j - t_j) + dice_weight p_j (g_j - sum_c p_c g_c);  0 at every other pixel.
+ *   Deviations: a batch without any valid pixel gives loss 0 and dlogits 0 (torch: NaN); a stray label is counted, not
+ *   refused (torch raises).
+ *   Two passes; the probabilities are never stored.  Pass 1 cuts the N HW pixels (frame-major) into chunks of 1024 and the
+ *   chunks into at most 1024 runs, one workgroup each: per chunk a thread forms maximum, sum of exponentials and CE term
+ *   of pixels t, t + 256, ...; wave w sums classes w, w + 4, ... (lane l: pixels l, l + 64, ... in order, then a butterfly);
+ *   chunks are added in chunk order, the runs by one block in run order.  Pass 2 recomputes the softmax per pixel.
+ *   scratch: kp2d_seg_loss_scratch_bytes(N, HW, C) bytes (0: bad shape), 16-byte aligned.
+ *
+ * kp2d_maxpool2_forward_train: y[n,c,i,j] = max of x[n,c,2i..2i+1,2j..2j+1], y [N, C, H / 2, W / 2] (floor), H, W >= 2.
+ * kp2d_maxpool2_backward: dx [N, C, H, W] from dy [N, C, H / 2, W / 2] and the forward's x: the gradient goes to the
+ *   window's maximum, found again from x (no index tensor).  Tie rule: the FIRST maximum in row-major order wins, torch's
+ *   rule (a later element replaces the maximum only when it is greater or NaN).  A last odd row or column gets 0.
+ * kp2d_shuffle_cat_forward: a [N, 4 C, h, w], b [N, Cb, 2 h, 2 w] (Cb >= 0) -> out [N, C + Cb, 2 h, 2 w]:
+ *       out[n, c, 2 i + u, 2 j + v] = a[n, 4 c + 2 u + v, i, j]  (torch's pixel_shuffle(2));  out[n, C + cb] = b[n, cb]
+ * kp2d_shuffle_cat_backward: da[n, 4 c + 2 u + v, i, j] = dout[n, c, 2 i + u, 2 j + v].  b's gradient is not formed: in the
+ *   head b is a frozen backbone map.  Both tensors have at most 2^38 elements (else KP2D_ERR_UNSUPPORTED).
+ *
+ *   Arithmetic: exact fp32 everywhere (no split-fp16, expf / logf of the device library).  Determinism: no float atomics;
+ *     every cut and every order of summation depends on the shapes alone, so all outputs are bit-identical from run to run. */
+size_t kp2d_conv_bias_scratch_bytes(int N, int H, int W, int Cin, int Cout);
+int kp2d_conv_bias_forward_train(const float* x, const float* w, const float* bias, int N, int H, int W, int Cin, int Cout, float* y,
+                                 void* scratch, size_t scratch_bytes, void* stream);
+int kp2d_conv_bias_backward(const float* x, const float* w, const float* dy, int N, int H, int W, int Cin, int Cout, float* d_weight,
+                            float* d_bias, float* dx /* may be NULL */, void* scratch, size_t scratch_bytes, void* stream);
+size_t kp2d_seg_loss_scratch_bytes(int N, int64_t HW, int C);
+int kp2d_seg_loss(const float* logits, const void* labels, int label_dtype, int N, int64_t HW, int C, int64_t ignore_index,
+                  double ce_weight, double dice_weight, float* loss, float* dlogits, int64_t* valid, int64_t* stray, void* scratch,
+                  size_t scratch_bytes, void* stream);
+int kp2d_maxpool2_forward_train(const float* x, int N, int C, int H, int W, float* y, void* stream);
+int kp2d_maxpool2_backward(const float* x, const float* dy, int N, int C, int H, int W, float* dx, void* stream);
+int kp2d_shuffle_cat_forward(const float* a, const float* b, int N, int C, int Cb, int h, int w, float* out, void* stream);
+int kp2d_shuffle_cat_backward(const float* dout, int N, int C, int Cb, int h, int w, float* da, void* stream);
+
 /* ---- Keypoint scores: repeatability, localisation error, matching score (nano-vs-slam_amd/csrc/keypoint_metrics.hip) ----
  * The counts and sums behind the reference's compute_repeatability (src/evaluation/detector.py:67-113) and
  * compute_matching_score (src/evaluation/descriptor.py:112-170), for B image pairs per call.  Stateless like the calls

@@ -11,6 +11,7 @@
 //
 // Tensors are planar [N, C, H, W] fp32.  The three convolution-shaped products are implicit GEMMs on
 // v_mfma_f32_16x16x4_f32 (exact fp32, bit for bit an fma chain); an output tile is 8 rows x 16 columns of the map.
+// hc_pack_kernel, hc_conv_kernel, hc_dw_kernel and hc_dw_sum_kernel live in train_conv.h, which seg_train.hip shares.
 //   hc_pack_kernel      w [Cout][Cin][3][3] -> [cin][tap][cout] as hc_conv_kernel stages it; the data gradient's form swaps
 //                       the channel axes and turns the taps by 180 degrees, so dx is the forward kernel run on dc
 //   hc_conv_kernel      grid (tiles, N): A = weights [16 cout][4 cin], B = input [4 cin][16 pixels of a row]; a wave owns two
@@ -40,129 +41,11 @@
 #include "device_guard.h"
 #include "mix64.h"
 #include "train_common.h"
+#include "train_conv.h"
 
 using namespace kp2d;
 
 namespace {
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
-constexpr int TH = 8, TW = 16;              // output tile: 8 rows (two per wave) x 16 columns (one MFMA N / K run)
-constexpr int HR = TH + 2, HC = TW + 2;     // halo tile
-constexpr int KC = 16;                      // input channels per chunk
-constexpr int MIN_CH = 16, MAX_CH = 128;
-constexpr int MAX_SLABS = 128;
-// LDS pitches in floats.  hc_conv_kernel: a wave's read is 16 consecutive pixels (or channels) for each of 4 input
-// channels: a channel pitch of 16 mod 64 spreads them over all 64 banks (halo plane 180 -> 208; weight rows Cout | 16,
-// whose 9-row channel stride is 16 or 48 mod 64).  hc_dw_kernel: 16 channels for each of 4 consecutive pixels: 4 mod 64.
-constexpr int IN_P = 208;
-constexpr int DW_DP = TH * TW + 4, DW_XP = 196;
-static_assert(IN_P >= HR * HC && IN_P % 64 == 16 && DW_XP >= HR * HC && DW_XP % 64 == 4 && DW_DP % 64 == 4, "LDS pitches");
-__host__ __device__ constexpr int cout_pitch(int co) { return co | 16; }
-constexpr size_t conv_lds_bytes(int co) { return (size_t)(KC * IN_P + KC * 9 * cout_pitch(co)) * sizeof(float); }
-constexpr size_t dw_lds_bytes(int co) { return (size_t)(co * DW_DP + KC * DW_XP) * sizeof(float); }
-static_assert(conv_lds_bytes(MAX_CH) == 96256 && dw_lds_bytes(MAX_CH) == 80128, "largest LDS images (of 160 KB)");
-
-// ---- weights as the conv kernel stages them ---------------------------------------------------------------------------
-// forward: wp[(ci 9 + t) Cout + co] = w[co][ci][t].  data gradient (its input channels are w's Cout, its output channels
-// w's Cin): wp[(co 9 + t) Cin + ci] = w[co][ci][8 - t].
-__global__ __launch_bounds__(256) void hc_pack_kernel(const float* __restrict__ w, float* __restrict__ wp, int Cout, int Cin, int dgrad) {
-  const int e = blockIdx.x * 256 + threadIdx.x;
-  if (e >= Cout * Cin * 9) return;
-  const int t = e % 9, ci = (e / 9) % Cin, co = e / (9 * Cin);
-  if (dgrad) wp[(co * 9 + (8 - t)) * Cin + ci] = w[e];
-  else wp[(ci * 9 + t) * Cout + co] = w[e];
-}
-
-struct ConvA {
-  const float* in;      // [N][CI][H][W]
-  const float* wp;      // [CI][9][CO]
-  const float* scale;   // [CO], or null: plain result into y_out
-  const float* shift;   // [CO]
-  float* c_out;         // [N][CO][H][W] conv result before the affine, or null
-  float* y_out;         // [N][CO][H][W]
-  int CI, H, W, tiles_x;
-  float slope;
-};
-
-template <int NT>      // CO = 16 NT output channels
-__global__ __launch_bounds__(256) void hc_conv_kernel(const ConvA a) {
-  extern __shared__ __attribute__((aligned(16))) float sm[];
-  constexpr int CO = NT * 16, COP = cout_pitch(CO);
-  float* s_in = sm;                 // [KC][IN_P]: plane c holds the 10 x 18 halo tile
-  float* s_w = sm + KC * IN_P;      // [KC * 9][COP]
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int j = lane & 15, k = lane >> 4;
-  const int H = a.H, W = a.W;
-  const int tx = blockIdx.x % a.tiles_x, ty = blockIdx.x / a.tiles_x, b = blockIdx.y;
-  const int y0 = ty * TH, x0 = tx * TW;
-  const size_t HW = (size_t)H * W;
-  const float* inb = a.in + (size_t)b * a.CI * HW;
-
-  f32x4 acc[2][NT];
-#pragma unroll
-  for (int m = 0; m < 2; ++m)
-#pragma unroll
-    for (int n = 0; n < NT; ++n) acc[m][n] = f32x4{0.f, 0.f, 0.f, 0.f};
-
-  const int nchunk = a.CI / KC;
-  for (int ch = 0; ch < nchunk; ++ch) {
-    __syncthreads();                // every wave is done with the previous chunk's images
-    for (int e = tid; e < KC * HR * HC; e += 256) {
-      const int c = e / (HR * HC), r = e - c * (HR * HC);
-      const int py = r / HC, px = r - py * HC;
-      const int gy = y0 - 1 + py, gx = x0 - 1 + px;
-      float v = 0.f;                // the zero padding, and the pixels of a ragged tile past the map
-      if (gy >= 0 && gy < H && gx >= 0 && gx < W) v = inb[(size_t)(ch * KC + c) * HW + (size_t)gy * W + gx];
-      s_in[c * IN_P + r] = v;
-    }
-    const float* wsrc = a.wp + (size_t)ch * KC * 9 * CO;
-    for (int e = tid; e < KC * 9 * CO; e += 256) {
-      const int row = e / CO, col = e - row * CO;
-      s_w[row * COP + col] = wsrc[e];
-    }
-    __syncthreads();
-#pragma unroll
-    for (int t = 0; t < 9; ++t) {
-      const int dy = t / 3, dx = t - 3 * (t / 3);
-#pragma unroll
-      for (int kk = 0; kk < KC / 4; ++kk) {
-        const int ci = 4 * kk + k;
-        float bv[2];
-#pragma unroll
-        for (int m = 0; m < 2; ++m) bv[m] = s_in[ci * IN_P + (2 * wave + m + dy) * HC + j + dx];
-#pragma unroll
-        for (int n = 0; n < NT; ++n) {
-          const float av = s_w[(ci * 9 + t) * COP + n * 16 + j];
-#pragma unroll
-          for (int m = 0; m < 2; ++m) acc[m][n] = __builtin_amdgcn_mfma_f32_16x16x4f32(av, bv[m], acc[m][n], 0, 0, 0);
-        }
-      }
-    }
-  }
-  // accumulator register r of lane (j, k): output channel 16 n + 4 k + r at pixel (y0 + 2 wave + m, x0 + j)
-  const int x = x0 + j;
-#pragma unroll
-  for (int m = 0; m < 2; ++m) {
-    const int y = y0 + 2 * wave + m;
-    if (y >= H || x >= W) continue;
-#pragma unroll
-    for (int n = 0; n < NT; ++n)
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const int co = 16 * n + 4 * k + r;
-        const size_t idx = ((size_t)b * CO + co) * HW + (size_t)y * W + x;
-        const float c = acc[m][n][r];
-        if (a.c_out) a.c_out[idx] = c;
-        float v = c;
-        if (a.scale) {
-          v = fmaf(c, a.scale[co], a.shift[co]);
-          v = v > 0.f ? v : a.slope * v;
-        }
-        a.y_out[idx] = v;
-      }
-  }
-}
 
 // ---- BatchNorm and activation backward of one channel plane ---------------------------------------------------------------
 __global__ __launch_bounds__(256) void hc_dpre_kernel(const float* __restrict__ dy, const float* __restrict__ y, const float* __restrict__ c,
@@ -198,110 +81,7 @@ __global__ __launch_bounds__(128) void hc_bn_sum_kernel(const float* __restrict_
   dgamma[co] = ordered_sum(part + (size_t)co * 2 + 1, (size_t)CO * 2, N);
 }
 
-// ---- weight gradient ------------------------------------------------------------------------------------------------------
-struct DwA {
-  const float* dc;      // [N][CO][H][W]
-  const float* x;       // [N][CI][H][W]
-  float* part;          // [slabs][CO][CI][9]
-  long long tiles, tps; // all tiles (frame-major), tiles per slab
-  int CI, H, W, tiles_x, tpf;
-};
-
-template <int NT>      // CO = 16 NT
-__global__ __launch_bounds__(256) void hc_dw_kernel(const DwA a) {
-  extern __shared__ __attribute__((aligned(16))) float sm[];
-  constexpr int CO = NT * 16, UNITS = 3 * NT, MAXU = (UNITS + 3) / 4;      // a unit: (16 output channels, tap row), 3 taps
-  float* s_dc = sm;                 // [CO][DW_DP]: the 8 x 16 tile of dc
-  float* s_x = sm + CO * DW_DP;     // [KC][DW_XP]: the 10 x 18 halo tile of this workgroup's 16 input channels
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int j = lane & 15, k = lane >> 4;
-  const int H = a.H, W = a.W, chunk = blockIdx.y;
-  const size_t HW = (size_t)H * W;
-
-  f32x4 acc[MAXU][3];
-#pragma unroll
-  for (int it = 0; it < MAXU; ++it)
-#pragma unroll
-    for (int kx = 0; kx < 3; ++kx) acc[it][kx] = f32x4{0.f, 0.f, 0.f, 0.f};
-
-  const long long t_begin = (long long)blockIdx.x * a.tps;
-  const long long t_end = t_begin + a.tps < a.tiles ? t_begin + a.tps : a.tiles;
-  for (long long tile = t_begin; tile < t_end; ++tile) {
-    const int b = (int)(tile / a.tpf), rem = (int)(tile - (long long)b * a.tpf);
-    const int ty = rem / a.tiles_x, tx = rem - ty * a.tiles_x;
-    const int y0 = ty * TH, x0 = tx * TW;
-    const float* dcb = a.dc + (size_t)b * CO * HW;
-    const float* xb = a.x + ((size_t)b * a.CI + (size_t)chunk * KC) * HW;
-    __syncthreads();
-    for (int e = tid; e < CO * TH * TW; e += 256) {
-      const int co = e >> 7, r = e & 127;
-      const int gy = y0 + (r >> 4), gx = x0 + (r & 15);
-      s_dc[co * DW_DP + r] = (gy < H && gx < W) ? dcb[(size_t)co * HW + (size_t)gy * W + gx] : 0.f;
-    }
-    for (int e = tid; e < KC * HR * HC; e += 256) {
-      const int c = e / (HR * HC), r = e - c * (HR * HC);
-      const int py = r / HC, px = r - py * HC;
-      const int gy = y0 - 1 + py, gx = x0 - 1 + px;
-      float v = 0.f;
-      if (gy >= 0 && gy < H && gx >= 0 && gx < W) v = xb[(size_t)c * HW + (size_t)gy * W + gx];
-      s_x[c * DW_XP + r] = v;
-    }
-    __syncthreads();
-    for (int s = 0; s < TH * TW / 4; ++s) {       // four pixels of a tile row per step, in pixel order
-      const int yy = s >> 2, xx = 4 * (s & 3) + k;
-#pragma unroll
-      for (int it = 0; it < MAXU; ++it) {
-        const int u = wave + 4 * it;
-        if (u < UNITS) {
-          const int n = u / 3, ky = u - 3 * n;
-          const float av = s_dc[(16 * n + j) * DW_DP + yy * TW + xx];
-#pragma unroll
-          for (int kx = 0; kx < 3; ++kx) {
-            const float bv = s_x[j * DW_XP + (yy + ky) * HC + xx + kx];
-            acc[it][kx] = __builtin_amdgcn_mfma_f32_16x16x4f32(av, bv, acc[it][kx], 0, 0, 0);
-          }
-        }
-      }
-    }
-  }
-  // register r of lane (j, k): output channel 16 n + 4 k + r, input channel 16 chunk + j
-  float* dst = a.part + (size_t)blockIdx.x * CO * a.CI * 9;
-#pragma unroll
-  for (int it = 0; it < MAXU; ++it) {
-    const int u = wave + 4 * it;
-    if (u < UNITS) {
-      const int n = u / 3, ky = u - 3 * n;
-#pragma unroll
-      for (int kx = 0; kx < 3; ++kx)
-#pragma unroll
-        for (int r = 0; r < 4; ++r)
-          dst[((size_t)(16 * n + 4 * k + r) * a.CI + chunk * KC + j) * 9 + ky * 3 + kx] = acc[it][kx][r];
-    }
-  }
-}
-
-__global__ __launch_bounds__(256) void hc_dw_sum_kernel(const float* __restrict__ part, float* __restrict__ dw, int slabs, int n) {
-  const int e = blockIdx.x * 256 + threadIdx.x;
-  if (e < n) dw[e] = ordered_sum(part + e, (size_t)n, slabs);
-}
-
 // ---- host ------------------------------------------------------------------------------------------------------------------
-struct Geo {
-  int tiles_x, tiles_y, tpf, slabs;
-  long long tiles, tps;
-};
-
-Geo geo_of(int N, int H, int W) {
-  Geo g{};
-  g.tiles_x = (W + TW - 1) / TW;
-  g.tiles_y = (H + TH - 1) / TH;
-  g.tpf = g.tiles_x * g.tiles_y;
-  g.tiles = (long long)N * g.tpf;
-  g.tps = (g.tiles + MAX_SLABS - 1) / MAX_SLABS;
-  g.slabs = (int)((g.tiles + g.tps - 1) / g.tps);
-  return g;
-}
-
 struct HeadPlan {
   float *wp, *dc, *bn, *dwp;
   size_t total;
@@ -331,54 +111,6 @@ const char* shape_problem(int N, int H, int W, int Cin, int Cout, int* code) {
     return "needs Cin % 16 == 0, Cout % 16 == 0 and 16 <= Cin, Cout <= 128";
   if ((int64_t)H * W > ((int64_t)1 << 30)) return "H * W above 2^30";
   return nullptr;
-}
-
-bool misaligned(const void* p, size_t a) { return (uintptr_t)p % a != 0; }
-
-template <int NT>
-int launch_conv_t(const ConvA& a, const dim3& grid, hipStream_t st) {
-  static PerDeviceOnce once;
-  if (int e = lds_opt_in(once, reinterpret_cast<const void*>(&hc_conv_kernel<NT>))) return e;
-  hipLaunchKernelGGL((hc_conv_kernel<NT>), grid, dim3(256), conv_lds_bytes(NT * 16), st, a);
-  return (int)hipGetLastError();
-}
-
-int launch_conv(const ConvA& a, int CO, int N, const Geo& g, hipStream_t st) {
-  const dim3 grid(g.tpf, N);
-  switch (CO / 16) {
-    case 1: return launch_conv_t<1>(a, grid, st);
-    case 2: return launch_conv_t<2>(a, grid, st);
-    case 3: return launch_conv_t<3>(a, grid, st);
-    case 4: return launch_conv_t<4>(a, grid, st);
-    case 5: return launch_conv_t<5>(a, grid, st);
-    case 6: return launch_conv_t<6>(a, grid, st);
-    case 7: return launch_conv_t<7>(a, grid, st);
-    case 8: return launch_conv_t<8>(a, grid, st);
-  }
-  return -1000;
-}
-
-template <int NT>
-int launch_dw_t(const DwA& a, const dim3& grid, hipStream_t st) {
-  static PerDeviceOnce once;
-  if (int e = lds_opt_in(once, reinterpret_cast<const void*>(&hc_dw_kernel<NT>))) return e;
-  hipLaunchKernelGGL((hc_dw_kernel<NT>), grid, dim3(256), dw_lds_bytes(NT * 16), st, a);
-  return (int)hipGetLastError();
-}
-
-int launch_dw(const DwA& a, int CO, const Geo& g, hipStream_t st) {
-  const dim3 grid(g.slabs, a.CI / KC);
-  switch (CO / 16) {
-    case 1: return launch_dw_t<1>(a, grid, st);
-    case 2: return launch_dw_t<2>(a, grid, st);
-    case 3: return launch_dw_t<3>(a, grid, st);
-    case 4: return launch_dw_t<4>(a, grid, st);
-    case 5: return launch_dw_t<5>(a, grid, st);
-    case 6: return launch_dw_t<6>(a, grid, st);
-    case 7: return launch_dw_t<7>(a, grid, st);
-    case 8: return launch_dw_t<8>(a, grid, st);
-  }
-  return -1000;
 }
 
 bool bad_slope(double s) { return !(s >= 0.0 && s < 1.0); }
@@ -539,7 +271,7 @@ int kp2d_cbr_forward_train(const float* x, const float* w, const float* scale, c
   ConvA a{};
   a.in = x; a.wp = p.wp; a.scale = scale; a.shift = shift; a.c_out = c; a.y_out = y;
   a.CI = Cin; a.H = H; a.W = W; a.tiles_x = g.tiles_x; a.slope = (float)slope;
-  if (int e = launch_conv(a, Cout, N, g, st)) return fail(KP2D_ERR_HIP, "cbr_forward_train: conv kernel: %d", e);
+  if (int e = launch_conv<false>(a, Cout, N, g, st)) return fail(KP2D_ERR_HIP, "cbr_forward_train: conv kernel: %d", e);
   return KP2D_OK;
 }
 
@@ -568,7 +300,7 @@ int kp2d_cbr_backward(const float* x, const float* w, const float* scale, const 
   HIP_TRY(hipGetLastError());
   DwA d{};
   d.dc = p.dc; d.x = x; d.part = p.dwp; d.tiles = g.tiles; d.tps = g.tps; d.CI = Cin; d.H = H; d.W = W; d.tiles_x = g.tiles_x; d.tpf = g.tpf;
-  if (int e = launch_dw(d, Cout, g, st)) return fail(KP2D_ERR_HIP, "cbr_backward: weight-gradient kernel: %d", e);
+  if (int e = launch_dw<false>(d, Cout, g, st)) return fail(KP2D_ERR_HIP, "cbr_backward: weight-gradient kernel: %d", e);
   const int nw = Cout * Cin * 9;
   hipLaunchKernelGGL(hc_dw_sum_kernel, dim3((nw + 255) / 256), dim3(256), 0, st, p.dwp, d_weight, g.slabs, nw);
   HIP_TRY(hipGetLastError());
@@ -577,7 +309,7 @@ int kp2d_cbr_backward(const float* x, const float* w, const float* scale, const 
     HIP_TRY(hipGetLastError());
     ConvA a{};
     a.in = p.dc; a.wp = p.wp; a.y_out = dx; a.CI = Cout; a.H = H; a.W = W; a.tiles_x = g.tiles_x;
-    if (int e = launch_conv(a, Cin, N, g, st)) return fail(KP2D_ERR_HIP, "cbr_backward: data-gradient kernel: %d", e);
+    if (int e = launch_conv<false>(a, Cin, N, g, st)) return fail(KP2D_ERR_HIP, "cbr_backward: data-gradient kernel: %d", e);
   }
   return KP2D_OK;
 }
@@ -609,7 +341,7 @@ int kp2d_cbr_forward_batchnorm(const float* x, const float* w, const float* gamm
   HIP_TRY(hipGetLastError());
   ConvA a{};      // the plain result, no affine
   a.in = x; a.wp = p.wp; a.y_out = c; a.CI = Cin; a.H = H; a.W = W; a.tiles_x = g.tiles_x;
-  if (int e = launch_conv(a, Cout, N, g, st)) return fail(KP2D_ERR_HIP, "cbr_forward_batchnorm: conv kernel: %d", e);
+  if (int e = launch_conv<false>(a, Cout, N, g, st)) return fail(KP2D_ERR_HIP, "cbr_forward_batchnorm: conv kernel: %d", e);
   hipLaunchKernelGGL(hb_plane_kernel, dim3(Cout, N), dim3(256), 0, st, c, p.bn, Cout, HW);
   HIP_TRY(hipGetLastError());
   hipLaunchKernelGGL(hb_stats_kernel, dim3(1), dim3(128), 0, st, p.bn, mean, invstd, running_mean, running_var, N, Cout, (float)HW,
@@ -651,7 +383,7 @@ int kp2d_cbr_backward_batchnorm(const float* x, const float* w, const float* gam
   HIP_TRY(hipGetLastError());
   DwA d{};
   d.dc = p.dc; d.x = x; d.part = p.dwp; d.tiles = g.tiles; d.tps = g.tps; d.CI = Cin; d.H = H; d.W = W; d.tiles_x = g.tiles_x; d.tpf = g.tpf;
-  if (int e = launch_dw(d, Cout, g, st)) return fail(KP2D_ERR_HIP, "cbr_backward_batchnorm: weight-gradient kernel: %d", e);
+  if (int e = launch_dw<false>(d, Cout, g, st)) return fail(KP2D_ERR_HIP, "cbr_backward_batchnorm: weight-gradient kernel: %d", e);
   const int nw = Cout * Cin * 9;
   hipLaunchKernelGGL(hc_dw_sum_kernel, dim3((nw + 255) / 256), dim3(256), 0, st, p.dwp, d_weight, g.slabs, nw);
   HIP_TRY(hipGetLastError());
@@ -660,7 +392,7 @@ int kp2d_cbr_backward_batchnorm(const float* x, const float* w, const float* gam
     HIP_TRY(hipGetLastError());
     ConvA a{};
     a.in = p.dc; a.wp = p.wp; a.y_out = dx; a.CI = Cout; a.H = H; a.W = W; a.tiles_x = g.tiles_x;
-    if (int e = launch_conv(a, Cin, N, g, st)) return fail(KP2D_ERR_HIP, "cbr_backward_batchnorm: data-gradient kernel: %d", e);
+    if (int e = launch_conv<false>(a, Cin, N, g, st)) return fail(KP2D_ERR_HIP, "cbr_backward_batchnorm: data-gradient kernel: %d", e);
   }
   return KP2D_OK;
 }

@@ -731,6 +731,25 @@ class _KP2DTinyBase(nn.Module):
             _lib.check(eng.lib.kp2d_set_tap(eng.handle, None, None, 0))
         return tap
 
+    def backbone_maps(self, x):
+        """Both maps the backbone hands to the dense heads, ``(x, skip)`` of the reference's ``self.backbone(x)``:
+        [B, c4, Hc, Wc] (the tap on ``backbone.conv4b``) and the full-resolution [B, c4, 2 Hc, 2 Wc] (the tap on
+        ``backbone.conv3b``), in the engine's current precision.  What ``seg_training.SegHeadTrainer.step_features`` takes.
+        The engine has one tap slot, so this runs TWO only-encoder forwards (backbone + VPR encoder, no other head), one per
+        tap: on a frozen backbone the maps are computed once per batch, not once per step."""
+        if x.dim() != 4 or x.shape[0] < 1:
+            raise ValueError(f"expected float32 [B >= 1, ., H, W] input, got {x.dtype} {tuple(x.shape)}")
+        B, _, H, W = x.shape
+        eng = self._get_engine(x.device)
+        c4, half = int(self.channel_dims[3]), self.cell // 2
+        skip = torch.full((B, c4, H // half, W // half), float("nan"), device=x.device)
+        _lib.check(eng.lib.kp2d_set_tap(eng.handle, b"backbone.conv3b", _ptr(skip), skip.numel()))
+        try:
+            self.only_encoder(x)
+        finally:
+            _lib.check(eng.lib.kp2d_set_tap(eng.handle, None, None, 0))
+        return self.backbone_features(x), skip
+
 
 def _common_init(self, *, nfeatures, device, channel_dims, bn_momentum, nClasses, num_clusters, downsample,
                  use_attention, mem_efficient, upscale_method, remove_netvlad, leaky_relu, depth, encoder_dim,
