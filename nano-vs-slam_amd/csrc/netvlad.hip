@@ -14,29 +14,15 @@
 #include "kp2d_kernels.h"
 #include "device_guard.h"
 #include "options.h"
+#include "netvlad_form.h"
 
 namespace kp2d {
 
-constexpr int VT = 64;  // pixels per LDS tile
+constexpr int VT = VLAD_VT;  // pixels per LDS tile
 
-int netvlad_nsplit(int S) {
-  // Depends on the frame size only: the order of the partial sums (and with it the last bits of the descriptor)
-  // must not change with the batch or sub-batch a frame happens to travel in (test_full_size_properties).
-  const int per = tuning().vlad_px;   // pixels per workgroup (tuning knob)
-  int n = (S + per - 1) / per;
-  return n < 1 ? 1 : n;
-}
-
-// Workgroups per slab.  1: a workgroup walks its whole slab.  > 1 (few frames per call, where nsplit workgroups per
-// frame would leave the chip idle): one workgroup per 64-pixel tile of the slab; the finish pass then adds the
-// tile partials of a slab in tile order before it adds the slabs — the same additions in the same order as a
-// workgroup walking the slab, so the result does not depend on which mode a frame was processed in.
-int netvlad_tiles_per_slab(int S, int B) {
-  const int ns = netvlad_nsplit(S);
-  if ((long)B * ns >= 256) return 1;
-  const int per = (S + ns - 1) / ns;
-  return (per + VT - 1) / VT;
-}
+// (slabs per frame, tiles per slab, the kernel choice and the ordered sum's branch: netvlad_form.h)
+int netvlad_nsplit(int S) { return netvlad_nsplit(S, tuning().vlad_px); }
+int netvlad_tiles_per_slab(int S, int B) { return netvlad_tiles_per_slab(S, B, tuning().vlad_px); }
 
 // NOWN = (cluster, channel) accumulators per thread: K*C <= 256*NOWN
 template <int NOWN>
@@ -379,8 +365,9 @@ __device__ __forceinline__ float vlad_ordered_sum(const VladArgs& a, int b, int 
   const float* base = a.part + (size_t)b * a.nsplit * tps * ps;
   auto slab = [&](int sp) {
     const float* q = base + (size_t)sp * tps * ps + e;
-    if (tps == 1) return q[0];
-    if (tps <= 8) {     // all tile partials in flight at once, then added in tile order
+    const int branch = netvlad_sum_branch(tps);
+    if (branch == VLAD_SUM_DIRECT) return q[0];
+    if (branch == VLAD_SUM_UNROLLED) {     // all tile partials in flight at once, then added in tile order
       float t[8];
 #pragma unroll
       for (int i = 0; i < 8; ++i) t[i] = i < tps ? q[(size_t)i * ps] : 0.f;
@@ -515,12 +502,12 @@ int launch_convap_pool(const PoolArgs& a, hipStream_t s) {
 }
 
 int launch_netvlad(const VladArgs& a, hipStream_t s) {
-  if (a.K > 64 || (a.K & 3) || (a.C & 3) || a.K * a.C > 8192 || a.K < 4) return -1100;
-  if ((a.K == 32 || a.K == 64) && a.C <= 64) {
-    const int kt = a.K / 32;
-    const bool split = a.prec == 1 && tuning().vlad_split;
-    const dim3 grid(a.nsplit * (a.tps > 1 ? a.tps : 1), a.B);
-    if (split) {
+  VladForm f;
+  if (int e = choose_netvlad(a.K, a.C, a.prec, tuning().vlad_split, f)) return e;
+  const dim3 grid(a.nsplit * (a.tps > 1 ? a.tps : 1), a.B);
+  if (f.kernel == VLAD_MFMA) {
+    const int kt = f.inst;
+    if (f.split) {
       const size_t lds = (size_t)(VT * VP + VT * AP + VT * HP) * sizeof(float);      // (hi | lo half images = HP floats per row)
       if (kt == 2) hipLaunchKernelGGL((netvlad_partial_mfma_kernel<2, true>), grid, dim3(256), lds, s, a);
       else hipLaunchKernelGGL((netvlad_partial_mfma_kernel<1, true>), grid, dim3(256), lds, s, a);
@@ -531,12 +518,12 @@ int launch_netvlad(const VladArgs& a, hipStream_t s) {
     }
   } else {
     const size_t lds1 = (size_t)(a.K * (a.C + 1) + VT * (a.C + 1) + VT * (a.K + 1)) * sizeof(float);
-    if (a.K * a.C <= 4096) {
-      hipLaunchKernelGGL(netvlad_partial_kernel<16>, dim3(a.nsplit * (a.tps > 1 ? a.tps : 1), a.B), dim3(256), lds1, s, a);
+    if (f.inst == 16) {
+      hipLaunchKernelGGL(netvlad_partial_kernel<16>, grid, dim3(256), lds1, s, a);
     } else {   // TINY_F: 64 clusters x 128 channels, 83 KB of LDS
       static PerDeviceOnce lds_once;      // per device: a handle may live on any visible device
       if (int e = lds_opt_in(lds_once, reinterpret_cast<const void*>(&netvlad_partial_kernel<32>))) return e;
-      hipLaunchKernelGGL(netvlad_partial_kernel<32>, dim3(a.nsplit * (a.tps > 1 ? a.tps : 1), a.B), dim3(256), lds1, s, a);
+      hipLaunchKernelGGL(netvlad_partial_kernel<32>, grid, dim3(256), lds1, s, a);
     }
   }
   const size_t lds2 = (size_t)(a.K * a.C + a.K + (a.K > FIN_T / 64 ? a.K : FIN_T / 64) + 8) * sizeof(float);
