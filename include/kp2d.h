@@ -740,6 +740,45 @@ int kp2d_maxpool2_backward(const float* x, const float* dy, int N, int C, int H,
 int kp2d_shuffle_cat_forward(const float* a, const float* b, int N, int C, int Cb, int h, int w, float* out, void* stream);
 int kp2d_shuffle_cat_backward(const float* dout, int N, int C, int Cb, int h, int w, float* da, void* stream);
 
+/* ---- Fine-tuning the depth head: the dense depth loss (nano-vs-slam_amd/csrc/depth_train.hip) ----
+ * What the reference's train_multitask.py moves in depth_head under _compute_depth_loss (KeypointNetwithIOLoss.py:907-916):
+ * SILogLoss (utils/losses.py:176-192) + huber_loss_factor torch.nn.HuberLoss().  In V2 non-attention models the head is the
+ * SegmentationHead with one class: the layers are the calls above (kp2d_conv_bias_* at Cout = 1) and kp2d_cbr_*, the update is
+ * kp2d_adam_step.  Stateless like those calls: caller-owned device buffers, the caller's stream, no synchronisation, no host
+ * round trip; every argument is checked on the host before the first launch; every output is fully written.
+ *
+ * kp2d_depth_loss: logits [N, HW] BEFORE the sigmoid, gt [N, HW], both fp32; 1 <= N <= 65535 and HW >= 1 (else KP2D_ERR_ARG),
+ *   HW <= 2^30 (else KP2D_ERR_UNSUPPORTED); silog_weight, huber_weight finite and >= 0 (the reference: 1 and 1).
+ *   A pixel is VALID when gt is finite and > 0 and the logit is finite.  A pixel whose gt or logit is not finite is STRAY: it is
+ *   treated as invalid and counted in *stray (kp2d_depth_sums' invalid-pixel rule; in torch one NaN poisons the batch).  Every
+ *   other pixel (gt <= 0) is ignored: the reference's mask = gt > 0.  *valid = M, the number of valid pixels.
+ *   Over the valid pixels, with p = sigmoid(z):
+ *       g_i = log p_i - log gt_i = -softplus(-z_i) - log gt_i          finite for every finite z (torch's log(sigmoid(z)) is
+ *                                                                      -inf in float32 beyond z = -104)
+ *       SILog = KP2D_SILOG_SCALE sqrt(Dg),  Dg = var(g) + KP2D_SILOG_LAMBDA mean(g)^2     (torch.var: unbiased, M - 1)
+ *       Huber = (1 / M) sum (0.5 d^2 if |d| < KP2D_HUBER_DELTA else KP2D_HUBER_DELTA (|d| - 0.5 KP2D_HUBER_DELTA)),  d = p - gt
+ *       loss  = silog_weight SILog + huber_weight Huber
+ *   -> *loss, parts[0] = SILog, parts[1] = Huber (unweighted), dlogits [N, HW] = d loss / d logits.  At a valid pixel
+ *       dlogits_i = silog_weight (KP2D_SILOG_SCALE / 2 / sqrt(Dg)) (2 (g_i - mean) / (M - 1) + 2 KP2D_SILOG_LAMBDA mean / M) (1 - p_i)
+ *                 + huber_weight (d_i if |d_i| < KP2D_HUBER_DELTA else sign(d_i) KP2D_HUBER_DELTA) / M  p_i (1 - p_i)
+ *   and 0 at every other pixel.  The three constants are the reference's and are no arguments.
+ *   Deviations: M = 0 gives loss 0 and dlogits 0 (torch: NaN); M = 1 gives SILog 0 with zero gradient, Huber stands alone
+ *   (torch's unbiased variance of one value is NaN); Dg = 0 gives SILog 0 with zero gradient (torch: a NaN gradient).
+ *   Two passes; nothing of size [N, HW] is stored besides dlogits.  Pass 1 cuts the N HW pixels (frame-major) into chunks of
+ *   1024 and the chunks into at most 1024 runs, one workgroup each.  The variance is never formed as E[g^2] - mean^2: a chunk
+ *   gives (count, mean, M2) - its sum of g, then its sum of (g - chunk mean)^2, each a float64 butterfly over a wave and the
+ *   four waves in wave order - and these are merged by Chan's formula in chunk order, then the runs in run order.  Per-pixel
+ *   arithmetic (g, p, d, the Huber term, dlogits) is fp32 with the device library's expf / logf / log1pf; the merge
+ *   accumulators, the Huber sum and g_i - mean are float64.  Pass 2 recomputes g and p per pixel.  No float atomics; every
+ *   cut depends on N and HW alone: all outputs are bit-identical from run to run.
+ *   scratch: kp2d_depth_loss_scratch_bytes(N, HW) bytes (0: bad shape), 16-byte aligned; a shorter one is KP2D_ERR_ARG. */
+#define KP2D_SILOG_SCALE 10.0
+#define KP2D_SILOG_LAMBDA 0.15
+#define KP2D_HUBER_DELTA 1.0
+size_t kp2d_depth_loss_scratch_bytes(int N, int64_t HW);
+int kp2d_depth_loss(const float* logits, const float* gt, int N, int64_t HW, double silog_weight, double huber_weight, float* loss,
+                    float* parts, float* dlogits, int64_t* valid, int64_t* stray, void* scratch, size_t scratch_bytes, void* stream);
+
 /* ---- Keypoint scores: repeatability, localisation error, matching score (nano-vs-slam_amd/csrc/keypoint_metrics.hip) ----
  * The counts and sums behind the reference's compute_repeatability (src/evaluation/detector.py:67-113) and
  * compute_matching_score (src/evaluation/descriptor.py:112-170), for B image pairs per call.  Stateless like the calls

@@ -199,75 +199,69 @@ def shuffle_cat_backward(dout, C):
     return da
 
 
-def _check_head(model, train):
-    """The refusals of ``SegHeadTrainer``, each with its reason -> the head's layers."""
+def _check_head(model, train, who="SegHeadTrainer", attr="seg_head", no_head=None):
+    """The refusals of a dense head's trainer (``who``, on ``model.<attr>``), each with its reason -> the head's layers."""
     if train not in ("head", "last"):
-        raise ValueError(f"SegHeadTrainer: train must be 'head' or 'last', got {train!r}")
-    head = getattr(model, "seg_head", None)
+        raise ValueError(f"{who}: train must be 'head' or 'last', got {train!r}")
+    head = getattr(model, attr, None)
     if head is None or not hasattr(head, "convs"):
-        raise ValueError("SegHeadTrainer: the model has no seg_head (the depth head is not trained)")
+        raise ValueError(no_head(model) if no_head else f"{who}: the model has no {attr} (the depth head is not trained)")
     if getattr(model, "_version_id", 2) != 2 or hasattr(head, "featB"):
-        raise ValueError("SegHeadTrainer: V3 heads are not supported: their last layer reads a channel slice of the trunk")
+        raise ValueError(f"{who}: V3 heads are not supported: their last layer reads a channel slice of the trunk")
     if getattr(model, "upscale_method", "pixelshuffle") != "pixelshuffle" or hasattr(head, "upsample"):
-        raise ValueError("SegHeadTrainer: upscale_method='convtranspose' (to_mcu) is not supported: only pixel shuffle has a backward")
+        raise ValueError(f"{who}: upscale_method='convtranspose' (to_mcu) is not supported: only pixel shuffle has a backward")
     attention = bool(getattr(model, "use_attention", False))
     if attention and train == "head":
-        raise ValueError("SegHeadTrainer: train='head' on an attention head is not supported (no attention backward exists); "
+        raise ValueError(f"{who}: train='head' on an attention head is not supported (no attention backward exists); "
                          "train='last' is")
     convs = list(head.convs)
     if len(convs) != (8 if attention else 9):
-        raise ValueError(f"SegHeadTrainer: unexpected head of {len(convs)} layers")
+        raise ValueError(f"{who}: unexpected head of {len(convs)} layers")
     last = convs[-1]
     if last.bias is None:
-        raise ValueError("SegHeadTrainer: the last layer has no bias")
+        raise ValueError(f"{who}: the last layer has no bias")
     Cout, Cin = last.weight.shape[:2]
     if Cin % 16 or not (MIN_CH <= Cin <= MAX_CH and 1 <= Cout <= MAX_CH):
-        raise ValueError(f"SegHeadTrainer: the last layer's channel counts ({Cin} -> {Cout}) are not supported by the conv kernels: "
+        raise ValueError(f"{who}: the last layer's channel counts ({Cin} -> {Cout}) are not supported by the conv kernels: "
                          f"needs Cin % 16 == 0, {MIN_CH} <= Cin <= {MAX_CH}, 1 <= Cout <= {MAX_CH}")
     if train == "head":
         for i, layer in enumerate(convs[:-1]):
             co, ci = layer.conv.weight.shape[:2]
             if ci % 16 or co % 16 or not (MIN_CH <= ci <= MAX_CH and MIN_CH <= co <= MAX_CH):
-                raise ValueError(f"SegHeadTrainer: seg_head.convs.{i} has channel counts {ci} -> {co}, which the conv kernels do not take "
+                raise ValueError(f"{who}: {attr}.convs.{i} has channel counts {ci} -> {co}, which the conv kernels do not take "
                                  f"(C % 16 == 0, {MIN_CH} <= C <= {MAX_CH}); train='last' does not run this layer")
         c_in, c_hidden, d1 = convs[0].conv.weight.shape[1], convs[0].conv.weight.shape[0], convs[4].conv.weight.shape[0]
         if d1 % 4 or convs[5].conv.weight.shape[1] != d1 // 4 + c_in or convs[6].conv.weight.shape[0] % 4 \
                 or convs[7].conv.weight.shape[1] <= convs[6].conv.weight.shape[0] // 4:
-            raise ValueError(f"SegHeadTrainer: the head's channel counts (c_in {c_in}, c_hidden {c_hidden}, d1 {d1}) do not chain")
+            raise ValueError(f"{who}: the head's channel counts (c_in {c_in}, c_hidden {c_hidden}, d1 {d1}) do not chain")
     return convs
 
 
-class SegHeadTrainer:
-    """Adam on ``model.seg_head`` under the reference's segmentation loss, on a frozen backbone.
+class _DenseHeadTrainer:
+    """The walk both dense heads' trainers share (``SegHeadTrainer`` here, ``depth_training.DepthHeadTrainer``): the V2
+    SegmentationHead's nine layers forward and backward, the checks of the model and of the maps, and the Adam loop.  A
+    trainer names its head (``_ATTR``), the prefix of its messages (``_WHO``) and what it calls the ground truth
+    (``_TARGET``), and supplies ``_check_target`` and ``_loss``."""
 
-        trainer = SegHeadTrainer(model, lr=1e-4, train="head", ce_weight=0.5, dice_weight=1.5, ignore_index=255)
-        loss = trainer.step(frames, labels)              # frames [N, 3, H, W]; labels [N, Hs, Ws] at the logits' size
-        x, skip = model.backbone_maps(frames)            # the frozen backbone, once
-        loss = trainer.step_features(x, skip, labels)    # a device scalar; no host synchronisation
-        logits = trainer.forward_features(x, skip)       # the training forward alone
+    _WHO = _ATTR = None
 
-    ``train="head"``: all nine layers of the V2 non-attention head, 26 tensors in the reference's registration order
-    (``convs.{0..7}.conv.weight``, ``.bn.weight``, ``.bn.bias``, ``convs.8.weight``, ``.bias``).  ``train="last"``: the last
-    layer's weight and bias alone, the reference's ``freeze_segmentation(except_last_layer=True)``; ``step`` then takes that
-    layer's input from the engine (a tap on the layer before it), so it also works on the V2 attention head, and
-    ``step_features(feat, None, labels)`` / ``forward_features(feat)`` take that input [N, c_hidden, Hs, Ws] directly.
-    BatchNorm runs on its running statistics, which stay as they are, and there is no dropout (``seg_head.eval()`` under
-    autograd).  V3 heads, an attention head in "head" mode, ``to_mcu`` models, channel counts the conv kernels do not take
-    (config N in "head" mode: its 72-channel concatenation) and odd backbone maps raise ValueError.  After a step every
-    updated parameter's version counter is bumped, so the engine re-packs its weights on its next call."""
-
-    def __init__(self, model, lr=1e-4, train="head", ce_weight=0.5, dice_weight=1.5, ignore_index=255, betas=(0.9, 0.999), eps=1e-8):
-        self.convs = _check_head(model, train)
+    def _init_walk(self, model, lr, train, betas, eps, no_head=None):
+        self.convs = _check_head(model, train, self._WHO, self._ATTR, no_head)
         if not (lr >= 0 and 0 <= betas[0] < 1 and 0 <= betas[1] < 1 and eps >= 0):
-            raise ValueError(f"SegHeadTrainer: lr {lr}, betas {betas}, eps {eps}")
-        if not (0 <= ce_weight < float("inf") and 0 <= dice_weight < float("inf")):
-            raise ValueError(f"SegHeadTrainer: ce_weight {ce_weight} and dice_weight {dice_weight} must be finite and >= 0")
+            raise ValueError(f"{self._WHO}: lr {lr}, betas {betas}, eps {eps}")
         self.model, self.train, self.lr, self.betas, self.eps = model, train, float(lr), tuple(betas), float(eps)
-        self.ce_weight, self.dice_weight, self.ignore_index = float(ce_weight), float(dice_weight), ignore_index
         self.slope = LEAKY_SLOPE if getattr(model, "leaky_relu", True) else 0.0
         self.steps = 0
         self.valid = self.stray = None      # int64 device scalars of the last step
         self._state = {}
+
+    def _check_target(self, target, shape, device):
+        """The ground truth against the logits' [N, Hs, Ws] -> what ``_loss`` takes; ValueError with the reason."""
+        raise NotImplementedError
+
+    def _loss(self, logits, target):
+        """-> (loss, dlogits); sets ``valid`` and ``stray``."""
+        raise NotImplementedError
 
     def parameters(self):
         """The trained parameters in the reference's registration order: 26 in "head" mode, 2 in "last" mode."""
@@ -286,25 +280,25 @@ class SegHeadTrainer:
 
     # ---- shapes ----------------------------------------------------------------------------------------------------------
     def _check_maps(self, x, skip):
-        last = self.convs[-1]
+        who, last = self._WHO, self.convs[-1]
         if self.train == "last":
             if skip is not None:
-                raise ValueError("SegHeadTrainer: in train='last' mode pass the last layer's input and skip=None")
-            _f32_maps("SegHeadTrainer", (("x", x),))
+                raise ValueError(f"{who}: in train='last' mode pass the last layer's input and skip=None")
+            _f32_maps(who, (("x", x),))
             if x.shape[1] != last.weight.shape[1]:
-                raise ValueError(f"SegHeadTrainer: the last layer reads [N, {last.weight.shape[1]}, Hs, Ws], got {tuple(x.shape)}")
+                raise ValueError(f"{who}: the last layer reads [N, {last.weight.shape[1]}, Hs, Ws], got {tuple(x.shape)}")
             return
         if skip is None:
-            raise ValueError("SegHeadTrainer: train='head' needs both backbone maps (model.backbone_maps)")
-        _f32_maps("SegHeadTrainer", (("x", x), ("skip", skip)))
+            raise ValueError(f"{who}: train='head' needs both backbone maps (model.backbone_maps)")
+        _f32_maps(who, (("x", x), ("skip", skip)))
         c_in = self.convs[0].conv.weight.shape[1]
         c_skip = self.convs[7].conv.weight.shape[1] - self.convs[6].conv.weight.shape[0] // 4
         N, _, H, W = x.shape
         if H % 2 or W % 2:
-            raise ValueError(f"SegHeadTrainer: the backbone map must have even height and width, got {H} x {W} "
+            raise ValueError(f"{who}: the backbone map must have even height and width, got {H} x {W} "
                              "(the pooled and shuffled map would not concatenate with it; the reference's own cat fails there)")
         if x.shape[1] != c_in or tuple(skip.shape) != (N, c_skip, 2 * H, 2 * W):
-            raise ValueError(f"SegHeadTrainer: needs x [N, {c_in}, H, W] and skip [N, {c_skip}, 2 H, 2 W], got {tuple(x.shape)}, {tuple(skip.shape)}")
+            raise ValueError(f"{who}: needs x [N, {c_in}, H, W] and skip [N, {c_skip}, 2 H, 2 W], got {tuple(x.shape)}, {tuple(skip.shape)}")
 
     def _cbr(self, i, x, scratch):
         layer = self.convs[i]
@@ -319,7 +313,7 @@ class SegHeadTrainer:
         cmax = max(max(l.conv.weight.shape[:2]) for l in self.convs[:-1])
         nbytes = int(lib.kp2d_cbr_train_scratch_bytes(N, skip.shape[2], skip.shape[3], cmax, cmax))
         if nbytes == 0:
-            raise ValueError(f"SegHeadTrainer: maps {tuple(x.shape)}, {tuple(skip.shape)} are not supported")
+            raise ValueError(f"{self._WHO}: maps {tuple(x.shape)}, {tuple(skip.shape)} are not supported")
         return _dev.scratch(nbytes, x.device)
 
     def _forward(self, x, skip):
@@ -350,16 +344,16 @@ class SegHeadTrainer:
         self._check_maps(x, skip)
         return self._forward(x, skip)[0]
 
-    def gradients(self, x, skip, labels):
+    def gradients(self, x, skip, target):
         """One forward, loss and backward without an update -> (loss, logits, the gradients in ``parameters()`` order)."""
         self._check_maps(x, skip)
         params = self.parameters()
         if not all(p.is_contiguous() for p in params):
-            raise ValueError("SegHeadTrainer: the head's parameters must be contiguous")
+            raise ValueError(f"{self._WHO}: the head's parameters must be contiguous")
         Hs, Ws = (x.shape[2], x.shape[3]) if self.train == "last" else (skip.shape[2], skip.shape[3])
-        _check_label_tensor("SegHeadTrainer", labels, (x.shape[0], Hs, Ws), x.device)
+        target = self._check_target(target, (x.shape[0], Hs, Ws), x.device)
         logits, a = self._forward(x, skip)
-        loss, dz, self.valid, self.stray = segmentation_loss(logits, labels, self.ce_weight, self.dice_weight, self.ignore_index)
+        loss, dz = self._loss(logits, target)
         last = self.convs[-1]
         head = self.train == "head"
         dw, db, dy = conv_bias_backward(a["feat"], last.weight, dz, need_dx=head)
@@ -384,10 +378,10 @@ class SegHeadTrainer:
         back(0, dy, need_dx=False)                                                           # (the backbone is frozen: no dx)
         return loss, logits, grads
 
-    def step_features(self, x, skip, labels):
-        """``model.backbone_maps`` of the frames ("last" mode: the last layer's input and None) and the labels -> the loss
-        before the update, a device scalar."""
-        loss, _, grads = self.gradients(x, skip, labels)
+    def step_features(self, x, skip, target):
+        """``model.backbone_maps`` of the frames ("last" mode: the last layer's input and None) and the ground truth -> the
+        loss before the update, a device scalar."""
+        loss, _, grads = self.gradients(x, skip, target)
         self.steps += 1
         for p, g in zip(self.parameters(), grads):
             m, v = self._moments(p)
@@ -396,18 +390,55 @@ class SegHeadTrainer:
                 torch.autograd.graph.increment_version(p)
         return loss
 
-    def step(self, frames, labels):
-        """Frames [N, 3, H, W] and labels [N, Hs, Ws] -> the loss before the update.  "head" mode runs the frozen backbone
-        through ``model.backbone_maps`` (two only-encoder forwards); "last" mode one full forward with a tap on the last
-        layer's input."""
+    def step(self, frames, target):
+        """Frames [N, 3, H, W] and the ground truth at the logits' size -> the loss before the update.  "head" mode runs the
+        frozen backbone through ``model.backbone_maps`` (two only-encoder forwards); "last" mode one full forward with a tap
+        on the last layer's input."""
         if not isinstance(frames, torch.Tensor) or not _is_device(frames):
-            raise ValueError("SegHeadTrainer.step: frames must be a device tensor (there is no CPU path)")
+            raise ValueError(f"{self._WHO}.step: frames must be a device tensor (there is no CPU path)")
         with torch.no_grad():
             if self.train == "head":
                 x, skip = self.model.backbone_maps(frames)
-                return self.step_features(x, skip, labels)
+                return self.step_features(x, skip, target)
             n = len(self.convs)
             half = self.model.cell // 2
             shape = (self.convs[-1].weight.shape[1], frames.shape[2] // half, frames.shape[3] // half)
-            _, feat = self.model.forward_with_tap(frames, f"seg_head.convs.{n - 2}", shape)
-        return self.step_features(feat, None, labels)
+            _, feat = self.model.forward_with_tap(frames, f"{self._ATTR}.convs.{n - 2}", shape)
+        return self.step_features(feat, None, target)
+
+
+class SegHeadTrainer(_DenseHeadTrainer):
+    """Adam on ``model.seg_head`` under the reference's segmentation loss, on a frozen backbone.
+
+        trainer = SegHeadTrainer(model, lr=1e-4, train="head", ce_weight=0.5, dice_weight=1.5, ignore_index=255)
+        loss = trainer.step(frames, labels)              # frames [N, 3, H, W]; labels [N, Hs, Ws] at the logits' size
+        x, skip = model.backbone_maps(frames)            # the frozen backbone, once
+        loss = trainer.step_features(x, skip, labels)    # a device scalar; no host synchronisation
+        logits = trainer.forward_features(x, skip)       # the training forward alone
+
+    ``train="head"``: all nine layers of the V2 non-attention head, 26 tensors in the reference's registration order
+    (``convs.{0..7}.conv.weight``, ``.bn.weight``, ``.bn.bias``, ``convs.8.weight``, ``.bias``).  ``train="last"``: the last
+    layer's weight and bias alone, the reference's ``freeze_segmentation(except_last_layer=True)``; ``step`` then takes that
+    layer's input from the engine (a tap on the layer before it), so it also works on the V2 attention head, and
+    ``step_features(feat, None, labels)`` / ``forward_features(feat)`` take that input [N, c_hidden, Hs, Ws] directly.
+    BatchNorm runs on its running statistics, which stay as they are, and there is no dropout (``seg_head.eval()`` under
+    autograd).  V3 heads, an attention head in "head" mode, ``to_mcu`` models, channel counts the conv kernels do not take
+    (config N in "head" mode: its 72-channel concatenation) and odd backbone maps raise ValueError.  After a step every
+    updated parameter's version counter is bumped, so the engine re-packs its weights on its next call.  The depth head of a
+    ``depth=True`` model is ``depth_training.DepthHeadTrainer``'s; this trainer never touches it."""
+
+    _WHO, _ATTR = "SegHeadTrainer", "seg_head"
+
+    def __init__(self, model, lr=1e-4, train="head", ce_weight=0.5, dice_weight=1.5, ignore_index=255, betas=(0.9, 0.999), eps=1e-8):
+        self._init_walk(model, lr, train, betas, eps)
+        if not (0 <= ce_weight < float("inf") and 0 <= dice_weight < float("inf")):
+            raise ValueError(f"SegHeadTrainer: ce_weight {ce_weight} and dice_weight {dice_weight} must be finite and >= 0")
+        self.ce_weight, self.dice_weight, self.ignore_index = float(ce_weight), float(dice_weight), ignore_index
+
+    def _check_target(self, labels, shape, device):
+        _check_label_tensor("SegHeadTrainer", labels, shape, device)
+        return labels
+
+    def _loss(self, logits, labels):
+        loss, dz, self.valid, self.stray = segmentation_loss(logits, labels, self.ce_weight, self.dice_weight, self.ignore_index)
+        return loss, dz
