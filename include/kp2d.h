@@ -244,7 +244,11 @@ int kp2d_get_precision(const kp2d_model* m);
 /* Parity aid: the next kp2d_forward calls also copy ONE intermediate activation, as planar [B,C,H,W] fp32, to dst
  * (device memory, capacity in floats; a forward that needs more fails with KP2D_ERR_ARG).  layer = a CBR's state-dict
  * prefix ("backbone.conv1a", "backbone.conv3b", "vlad_head.convlad3", ...; a layer whose MaxPool2d is folded into its
- * store yields the pooled tensor) or "<attention module>.att" / ".mff" (modules/segformer.py:217-220).  This is how
+ * store yields the pooled tensor), "<attention module>.att" / ".mff" (modules/segformer.py:217-220), or a stage inside an
+ * attention module: its 1x1 layers by their state-dict prefix ("<module>.att.fn.to_q", ".att.fn.to_out", ".mff.fn.net.0",
+ * ".mff.fn.net.1.net.1", ".mff.fn.net.3"), ".att.norm" / ".mff.norm" (the LayerNorm outputs), ".att.fn.to_kv" [2C, H/2, W/2],
+ * ".att.fn" (the attention output in front of to_out) and ".mff.fn.net.1.net.0" (the depthwise output; three-launch MixFFN
+ * only, the fused tail never writes it).  This is how
  * the tests compare the kernels with the reference's recorded intermediates (tests/golden *_taps fixtures) layer by
  * layer.  layer = NULL or dst = NULL switches it off. */
 int kp2d_set_tap(kp2d_model* m, const char* layer, float* dst, size_t capacity_floats);

@@ -306,6 +306,7 @@ Act Plan::layernorm(const std::string& prefix, const Act& in) {
 Act Plan::attention_module(const std::string& p, const Act& x, bool pool) {
   const int C = x.C, h = x.H, w = x.W;
   Act ln1 = layernorm(p + ".att.norm", x);
+  tap(p + ".att.norm", ln1);
   Act q = pw(p + ".att.fn.to_q", ln1, ACT_NONE);
   Act kv = alloc(2 * C, h / 2, w / 2);
   {
@@ -316,6 +317,7 @@ Act Plan::attention_module(const std::string& p, const Act& x, bool pool) {
     if (s1.p) s1.p += (long)w * C;
     conv_src(p + ".att.fn.to_kv", s0, s1, ACT_NONE, ST_NHWC, 0, h / 2, w / 2, out(kv));
   }
+  tap(p + ".att.fn.to_kv", kv);
   release(ln1);
   Act ao = alloc(C, h, w);
   {
@@ -329,12 +331,14 @@ Act Plan::attention_module(const std::string& p, const Act& x, bool pool) {
       return launch_attention(a, stream);
     });
   }
+  tap(p + ".att.fn", ao);      // the attention output in front of to_out
   release(q);
   release(kv);
   Act t = pw(p + ".att.fn.to_out", ao, ACT_NONE);
   release(ao);
   tap(p + ".att", t);
   Act ln2 = layernorm(p + ".mff.norm", t);
+  tap(p + ".mff.norm", ln2);
   release(t);
   Act f0 = pw(p + ".mff.fn.net.0", ln2, ACT_NONE);
   release(ln2);
@@ -354,6 +358,7 @@ Act Plan::attention_module(const std::string& p, const Act& x, bool pool) {
     });
   }
   release(f0);
+  tap(p + ".mff.fn.net.1.net.0", f1);      // (three-launch path only: the fused tail never writes this tensor)
   Act f2 = pw(p + ".mff.fn.net.1.net.1", f1, ACT_GELU);
   release(f1);
   Act f3 = pw(p + ".mff.fn.net.3", f2, ACT_NONE, pool ? ST_NHWC_POOL : ST_NHWC);

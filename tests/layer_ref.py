@@ -52,6 +52,11 @@ SPLIT_REL = 3 * 2.0 ** -22   # dx w + x dw + xl wl
 SPLIT_FLOOR = 2.0 ** -25     # subnormal xl: half the fp16 subnormal spacing
 OUT_LINEAR = 2.0 ** -23
 OUT_TRANSCENDENTAL = 2.0 ** -21
+GELU_SLOPE = 1.13            # max |d gelu / dx| = 1.1290 (at x = sqrt 2)
+# conv_common.h gelu_fast (erf by Abramowitz & Stegun 7.1.26 with v_rcp_f32 and v_exp_f32) against the exact-erf GELU, relative
+# to |x|: tests/test_attention_head_ref_cpu.py measures 3.00e-07 (at x = 0.055) for a numpy float32 emulation over a dense grid of
+# [-12, 12]; twice that for the two hardware approximations (1 ulp each), which numpy computes correctly rounded
+GELU_ERR = 6.0e-7
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 POLICY_H = os.path.join(ROOT, "nano-vs-slam_amd", "csrc", "conv_policy.h")
@@ -59,13 +64,12 @@ POLICY_H = os.path.join(ROOT, "nano-vs-slam_amd", "csrc", "conv_policy.h")
 # profile kernel families that are convolutions (kp2d_profile_get); everything a case's profile lists under one of these
 # must be compared or excluded below
 CONV_FAMILIES = ("conv3x3_f16x3", "conv1x1_f16x3", "conv3x3_f32<", "conv1x1_f32", "conv3x3_head", "conv1a")
-SPLIT_FAMILIES = ("conv3x3_f16x3", "conv1x1_f16x3", "conv1a_mfma")
+# the other launches of the attention segmentation head (tests/attention_head_ref.py)
+HEAD_FAMILIES = ("channel_layernorm", "attention", "dwconv3x3", "mff_tail")
+SPLIT_FAMILIES = ("conv3x3_f16x3", "conv1x1_f16x3", "conv1a_mfma", "attention_f16x3", "mff_tail")
 
 # conv launches this module does not model, with the tests that cover them
 EXCLUDED = {
-    r"\.att\.fn\.": "attention 1x1 / 2x2 projections: test_gpu_parity.py test_intermediate_taps_on_device (.att taps), "
-                    "test_precision_modes_agree_on_other_shapes",
-    r"\.mff\.fn\.": "MixFFN 1x1 layers: test_mixffn_tail_as_one_launch_equals_the_three_launches, .mff taps",
     r"^vlad_head\.netvlad": "NetVLAD / ConvAP pooling: test_against_reference_golden (vlad), test_against_oracle_other_shapes",
 }
 
@@ -89,18 +93,21 @@ class Spec:
     transform: None, "pool" (maxpool2 of the tap) or (c0, c1) (a channel slice).  out: ("tap", name) or
     ("api", [(key, c0, c1), ...]) — the API tensors the layer writes and which of its channels go there."""
 
-    def __init__(self, name, srcs, bn=True, act="leaky", post=None, out=None):
+    def __init__(self, name, srcs, bn=True, act="leaky", post=None, out=None, launch=None):
         self.name, self.srcs, self.bn, self.act, self.post = name, srcs, bn, act, post
         self.out = out or ("tap", name)
+        self.launch = launch or name      # the layer name the profile lists the launch under
 
     def weight_key(self):
         return f"{self.name}.conv.weight" if self.bn else f"{self.name}.weight"
 
 
 def layer_graph(cfg):
-    """{layer name: Spec} for the V2 / V3 configurations without attention and with PixelShuffle upsampling."""
-    if cfg["use_attention"] or cfg["upscale_method"] != "pixelshuffle" or cfg.get("depth") or cfg["in_channels"] != 3:
-        raise NotImplementedError("layer_ref models the plain V2 / V3 configurations")
+    """{layer name: Spec} for the V2 / V3 configurations with PixelShuffle upsampling.  The attention configurations add the
+    stages of tests/attention_head_ref.py (LayerNorm, attention, depthwise 3x3, the fused MixFFN tail) between the conv layers
+    of their segmentation head; both MixFFN paths are in the graph, the profile says which one ran."""
+    if cfg["upscale_method"] != "pixelshuffle" or cfg.get("depth") or cfg["in_channels"] != 3:
+        raise NotImplementedError("layer_ref models the V2 / V3 configurations with PixelShuffle upsampling")
     lk = "leaky" if cfg["leaky_relu"] else "relu"
     ds = cfg["downsample"]
     g = {}
@@ -134,19 +141,28 @@ def layer_graph(cfg):
         add("desc_head.confBb", [("desc_head.confAa", None)], bn=False, act="none", out=("api", [("feat", 0, cfg["nfeatures"])]))
     L = "seg_head.convs."
     add(L + "0", xb)
-    add(L + "1", [(L + "0", None)], post="pool")
-    add(L + "2", [(L + "1", None)])
-    add(L + "3", [(L + "2", None)])
-    add(L + "4", [(L + "3", None)], post="shuffle")
-    add(L + "5", [(L + "4", None)] + xb)
-    add(L + "6", [(L + "5", None)], post="shuffle")
-    add(L + "7", [(L + "6", None), skip])
+    if cfg["use_attention"]:      # oracle seg_trunk, attention branch: CBR, module (+ pool), module, CBR + shuffle, ...
+        import attention_head_ref as A
+        A.add_module(g, L + "1", L + "0", pool=True)
+        A.add_module(g, L + "2", L + "1.mff", pool=False)
+        add(L + "3", [(L + "2.mff", None)], post="shuffle")
+        i = 4
+    else:
+        add(L + "1", [(L + "0", None)], post="pool")
+        add(L + "2", [(L + "1", None)])
+        add(L + "3", [(L + "2", None)])
+        add(L + "4", [(L + "3", None)], post="shuffle")
+        i = 5
+    add(L + str(i), [(L + str(i - 1), None)] + xb)
+    add(L + str(i + 1), [(L + str(i), None)], post="shuffle")
+    add(L + str(i + 2), [(L + str(i + 1), None), skip])
+    trunk, last = L + str(i + 2), L + str(i + 3)
     if cfg["v3"]:
         half = cfg["channel_dims"][4] // 2
-        add("seg_head.featB", [(L + "7", (0, half))], bn=False, act="none", out=("api", [("feat", 0, cfg["nfeatures"])]))
-        add(L + "8", [(L + "7", (-half, None))], bn=False, act="softmax", out=("api", [("seg", 0, None)]))
+        add("seg_head.featB", [(trunk, (0, half))], bn=False, act="none", out=("api", [("feat", 0, cfg["nfeatures"])]))
+        add(last, [(trunk, (-half, None))], bn=False, act="softmax", out=("api", [("seg", 0, None)]))
     else:
-        add(L + "8", [(L + "7", None)], bn=False, act="none", out=("api", [("seg", 0, None)]))
+        add(last, [(trunk, None)], bn=False, act="none", out=("api", [("seg", 0, None)]))
     add("vlad_head.convlad1", xb)
     add("vlad_head.convlad2", [("vlad_head.convlad1", None)])
     add("vlad_head.convlad3", [("vlad_head.convlad2", None)])
@@ -156,7 +172,7 @@ def layer_graph(cfg):
 def merged_parts(cfg):
     """The layers the merged first launch of the heads ("heads.first", model_desc.cpp describe()) computes."""
     parts = ["score_loc_head.convDa"] if cfg["v3"] else ["score_head.convDa", "loc_head.convDa", "desc_head.convA"]
-    return parts + ["seg_head.convs.0", "vlad_head.convlad1"]
+    return parts + ([] if cfg["use_attention"] else ["seg_head.convs.0"]) + ["vlad_head.convlad1"]
 
 
 def tap_shapes(cfg, sd, H, W):
@@ -173,8 +189,13 @@ def tap_shapes(cfg, sd, H, W):
         return c, h, w
 
     for name, sp in g.items():          # (insertion order is a topological order)
+        if hasattr(sp, "shape"):        # a stage of attention_head_ref
+            shp[name] = sp.shape([src_shape(*s) for s in sp.srcs])
+            continue
         _, h, w = src_shape(*sp.srcs[0])
         co = sd[sp.weight_key()].shape[0]
+        if sd[sp.weight_key()].shape[-1] == 2:      # the 2 x 2 stride-2 to_kv
+            h, w = h // 2, w // 2
         if sp.post == "pool":
             h, w = h // 2, w // 2
         elif sp.post == "shuffle":
@@ -199,11 +220,13 @@ def fold(sd, sp):
     return s, (beta - mu * s).astype(np.float32)
 
 
-def pre_activation(x, w, s, sh, split):
-    """z64 * s + sh and its bound for planar inputs x [C, H, W] (float64) and weights w [Co, C, 3, 3] (or [Co, C, 1, 1])."""
+def pre_activation(x, w, s, sh, split, b_in=None):
+    """z64 * s + sh and its bound for planar inputs x [C, H, W] (float64) and weights w [Co, C, 3, 3] ([Co, C, 1, 1], or the
+    [Co, C, 2, 2] of a stride-2 conv).  b_in: a bound on the error the input itself carries (a stage computed inside the same
+    launch): a linear layer passes it on as |s| conv(b_in, |w|)."""
     x = np.asarray(x, np.float64)[None]
     w = np.asarray(w, np.float64)
-    conv = orc.conv2d_3x3 if w.shape[-1] == 3 else orc.conv2d_1x1
+    conv = {3: orc.conv2d_3x3, 2: orc.conv2d_2x2_s2, 1: orc.conv2d_1x1}[w.shape[-1]]
     z = conv(x, w)[0]
     M = conv(np.abs(x), np.abs(w))[0]
     s64, sh64 = s.astype(np.float64)[:, None, None], sh.astype(np.float64)[:, None, None]
@@ -212,6 +235,8 @@ def pre_activation(x, w, s, sh, split):
         ones = np.ones((1, 1) + x.shape[2:])
         W1 = conv(ones, np.abs(w).sum(axis=1, keepdims=True))[0]
         b = b + SPLIT_REL * M + SPLIT_FLOOR * W1
+    if b_in is not None:
+        b = b + conv(np.asarray(b_in, np.float64)[None], np.abs(w))[0]
     return z * s64 + sh64, np.abs(s64) * b
 
 
@@ -229,6 +254,10 @@ def activate(pre, b, act):
         y = np.tanh(pre)
     elif act == "sig0tanh":
         y = np.concatenate([1.0 / (1.0 + np.exp(-pre[:1])), np.tanh(pre[1:])])
+    elif act == "gelu":
+        # exact-erf GELU; |d gelu / dx| <= 1.13, and the device's gelu_fast is GELU_ERR |x| away from it
+        y = orc.gelu_erf(pre)
+        return y, GELU_SLOPE * b + GELU_ERR * np.abs(pre) + OUT_LINEAR * np.abs(y)
     elif act == "softmax":
         e = np.exp(pre - pre.max(axis=0, keepdims=True))
         y = e / e.sum(axis=0, keepdims=True)
@@ -259,6 +288,8 @@ def source(tap, tr):
 def reference(sp, inputs, sd, split):
     """Float64 output of layer `sp` for ONE frame and its per-element bound.  inputs: the planar [C, H, W] taps named by
     sp.srcs, in order; split: the launch ran the split-fp16 arithmetic."""
+    if hasattr(sp, "ref"):          # a stage of attention_head_ref
+        return sp.ref([source(t, tr) for t, (_, tr) in zip(inputs, sp.srcs)], sd, split)
     x = np.concatenate([source(t, tr) for t, (_, tr) in zip(inputs, sp.srcs)], axis=0)
     s, sh = fold(sd, sp)
     pre, b = pre_activation(x, sd[sp.weight_key()], s, sh, split)
