@@ -783,6 +783,72 @@ size_t kp2d_depth_loss_scratch_bytes(int N, int64_t HW);
 int kp2d_depth_loss(const float* logits, const float* gt, int N, int64_t HW, double silog_weight, double huber_weight, float* loss,
                     float* parts, float* dlogits, int64_t* valid, int64_t* stray, void* scratch, size_t scratch_bytes, void* stream);
 
+/* ---- Fine-tuning the keypoint heads: the self-supervised keypoint loss (nano-vs-slam_amd/csrc/keypoint_train.hip) ----
+ * The first block of the reference's KeypointNetwithIOLoss.forward (KeypointNetwithIOLoss.py:423-541, build_descriptor_loss
+ * :25-154) with with_io = False, over B pairs of a frame (the TARGET view, the reference's out) and its augmented view (the
+ * SOURCE view, out_aug), with its gradient.  The heads' layers are kp2d_cbr_*, kp2d_conv_bias_* and kp2d_shuffle_cat_*, the
+ * update is kp2d_adam_step.  Stateless like those calls: caller-owned device buffers, the caller's stream, no
+ * synchronisation, no host round trip; every argument is checked on the host before the first launch; every output is
+ * fully written.  Non-finite inputs are the caller's problem: nothing is read or written out of bounds because of them, but
+ * the values are then undefined.
+ *
+ * kp2d_keypoint_loss: per view, fp32 planar, as the model's training forward returns them: score [B,1,Hc,Wc] after the
+ *   sigmoid, shift [B,2,Hc,Wc] after the tanh (channel 0: x), feat [B,C,Hf,Wf], the raw descriptor map (Hf x Wf is free).
+ *   homography [B,3,3] fp32, row-major, in NORMALISED coordinates ([-1, 1] over [0, W-1] x [0, H-1]): it maps source points
+ *   to target points (the reference's _warp_homography_batch).  N = Hc Wc cells, numbered row-major; cell i is INTERIOR when
+ *   it is not on the outermost ring; n = (Hc - 2)(Wc - 2) interior cells (0 if Hc < 3 or Wc < 3).
+ *   Decode (post_processing in training mode), per view:  score' = score at interior cells, 0 on the ring;
+ *       u = cell (col, row) + step + shift cross_ratio step,  step = (cell - 1) / 2;  coord = (clamp(u.x, 0, W-1), clamp(u.y, 0, H-1));
+ *       the clamp's gradient is 1 where 0 <= u <= size - 1 (closed) and 0 elsewhere.  feat is not sampled here.
+ *   Warp:  norm(c) = (c.x / ((W-1)/2) - 1, c.y / ((H-1)/2) - 1);  (X, Y, Z) = Hom (norm(coord_src_i), 1);
+ *       wn_i = (X / Z, Y / Z);  w_i = ((wn_i.x + 1)(W-1)/2, (wn_i.y + 1)(H-1)/2).
+ *   Location:  d_i = min_j |w_i - coord_tgt_j|_2 over ALL N target cells, a_i its argmin;  valid_i = d_i < KP2D_KEYPOINT_VALID_DIST
+ *       and i interior;  M = the number of valid cells of the whole batch;  loc = (1 / M) sum_valid d_i.  d d_i / d w_i =
+ *       (w_i - coord_tgt_a) / d_i = - d d_i / d coord_tgt_a, and 0 at d_i = 0 (torch's norm).
+ *   USP:  S_i = score'_tgt[a_i] + score'_src[i];  usp = (1 / M) sum_valid S_i (d_i - loc);  d usp / d S_i = (d_i - loc) / M,
+ *       d usp / d d_i = (S_i - mean_valid S) / M.
+ *   Consistency:  v_i = bilinear sample of score'_tgt at wn_i (zeros outside, align_corners = True, the grid detached);
+ *       con = 2 / (B n) sum_interior (v_i - score_src[i])^2  (0 when n = 0).
+ *   Descriptor, per pair, only when n >= KP2D_KEYPOINT_MIN_ANCHORS, over the interior cells k (row-major) as anchors:
+ *       ref_k = bilinear sample of feat_src at norm(coord_src_k), tar_k = of feat_tgt at wn_k (grids detached), each
+ *       normalised as x / (|x + 1e-8|_2 + 1e-8);  dmat_kj = sqrt(2 - 2 clamp(ref_k . tar_j, -1, 1) + 1e-8);
+ *       best_k = argmin_j dmat_kj;  hit_k = (w_best == w_k, both components exactly);
+ *       neg_k = argmin_j dmat_kj over the columns with NOT (|w_j.x - w_k.x| <= relax_field and |w_j.y - w_k.y| <= relax_field);
+ *       t_k = max(KP2D_KEYPOINT_MARGIN + |ref_k - tar_k + 1e-6|_2 - |ref_k - tar_neg + 1e-6|_2, 0)   (torch's triplet_margin_loss);
+ *       metric = (1 / B) sum_pairs (1 / n) sum_k t_k.  Its gradient reaches ref_k, tar_k and tar_neg, then the two feat maps
+ *       through the normalisation and the bilinear sampling; it reaches no coordinate.
+ *   Total:  loss = keypoint_weight (loc_weight loc + descriptor_weight 2 metric + score_weight usp + score_weight con).
+ *   -> *loss; parts[4] = (loc, metric, usp, con), unweighted; dscore_t, dshift_t, dfeat_t, dscore_s, dshift_s, dfeat_s shaped
+ *   like the six maps: d loss / d map; counts[3] int64 = (M, n if the descriptor term ran else 0, sum over the pairs of hit_k);
+ *   recall = counts[2] / (B n).
+ *   Rules the reference leaves open:  every argmin takes the LOWEST index among equal values (a_i compares squared distances;
+ *   torch's min and unstable sort define none);  an anchor with no admissible column takes best_k as neg_k (the reference's
+ *   outcome under a stable sort);  M = 0 gives loc = usp = 0 with zero gradients (torch: NaN);  the IO-net term (with_io,
+ *   InlierNet) is not built.
+ *   Arithmetic: fp32 throughout, exact: the n x n x C products run on v_mfma_f32_16x16x4_f32 (an fmaf chain over the
+ *   channels in ascending order) fused with both running argmins, nothing of size n x n is stored; the N x N nearest search
+ *   is tiled through LDS.  The sums over cells behind M, loc, mean S, usp, con and the hinge sum are float64, per pair by a
+ *   strided walk and a fixed butterfly, then over the pairs in pair order; so are the per-anchor reductions over the channels
+ *   (the two norms of the normalisation and of the triplet term, sum g x of the normalisation's backward), O(n C) work.  No float atomics: where several anchors reach one
+ *   target cell (through a_i, neg_k, or the bilinear backward onto score_tgt and the feat maps) the receiving side scans the
+ *   anchors in ascending order.  Every order depends on the shapes alone: all outputs are bit-identical from run to run.
+ *   Coupling between the pairs of a batch: M, loc and mean S (so dshift_*, and the usp part of dscore_*) are batch-wide; the
+ *   descriptor term's dfeat_* carry the factor 1 / B and the consistency part of dscore_* the factor 1 / (B n), nothing else:
+ *   a pair gives the same dfeat bits alone and in a batch of B = 2^k, up to that factor.
+ *   Supported: 1 <= B <= 65535, N <= 65536, C a multiple of 16 in [16, 256], Hf Wf <= 2^24 (else KP2D_ERR_UNSUPPORTED);
+ *   H, W >= 2, cell >= 1, cross_ratio, relax_field and the weights finite and >= 0 (else KP2D_ERR_ARG).
+ *   scratch: kp2d_keypoint_loss_scratch_bytes(B, Hc, Wc, C, Hf, Wf) bytes (0: unsupported shape), 16-byte aligned. */
+#define KP2D_KEYPOINT_VALID_DIST 4.0
+#define KP2D_KEYPOINT_MARGIN 0.2
+#define KP2D_KEYPOINT_MIN_ANCHORS 20
+size_t kp2d_keypoint_loss_scratch_bytes(int B, int Hc, int Wc, int C, int Hf, int Wf);
+int kp2d_keypoint_loss(const float* score_t, const float* shift_t, const float* feat_t, const float* score_s, const float* shift_s,
+                       const float* feat_s, const float* homography, int B, int Hc, int Wc, int C, int Hf, int Wf, int H, int W,
+                       int cell, double cross_ratio, double relax_field, double loc_weight, double descriptor_weight,
+                       double score_weight, double keypoint_weight, float* loss, float* parts, float* dscore_t, float* dshift_t,
+                       float* dfeat_t, float* dscore_s, float* dshift_s, float* dfeat_s, int64_t* counts, void* scratch,
+                       size_t scratch_bytes, void* stream);
+
 /* ---- Keypoint scores: repeatability, localisation error, matching score (nano-vs-slam_amd/csrc/keypoint_metrics.hip) ----
  * The counts and sums behind the reference's compute_repeatability (src/evaluation/detector.py:67-113) and
  * compute_matching_score (src/evaluation/descriptor.py:112-170), for B image pairs per call.  Stateless like the calls
