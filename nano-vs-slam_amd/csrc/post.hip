@@ -8,11 +8,16 @@
 //  * topk_kernel       the callers' selectors: score > thr, then the k best,
 //                      ordered (score desc, flat index asc) — the order of torch.topk in
 //                      gluefactory/models/extractors/kp2dtiny.py:40; K1/K2 use the same SET.
-// Every float op that feeds an index decision is written with explicit round-to-nearest
-// intrinsics so hipcc's default fp-contraction cannot fuse it differently from the reference.
+// Every float op that feeds an index decision is written in the reference's order with the round-to-nearest intrinsics.
+// Those are plain operators to hipcc, so its default fp-contraction still fuses a product into the sum it feeds: the
+// decoded coordinate (base + sx * gain) and the three sums of the bilinear sample are fused multiply-adds, one rounding
+// fewer than the reference's float32 each — never more error, but not its bits.  The chain from the stored coordinate to
+// the sample index (divide, -1, +1, * 0.5, * (size - 1)) has no product feeding a sum and rounds as the reference does.
+// tests/post_select_ref.py bounds every output against float64 per element and checks the index decisions exactly.
 #include "conv_common.h"
 #include "device_guard.h"
 #include "options.h"
+#include "select_form.h"
 
 namespace kp2d {
 
@@ -154,8 +159,8 @@ __global__ __launch_bounds__(256) void post_seg_kernel(const PostArgs a, const A
 }
 
 int launch_post_seg(const PostArgs& a, const ArgmaxArgs& g, hipStream_t s) {
-  const bool quad = (g.HW & 3) == 0 && ((uintptr_t)g.seg & 15) == 0 && ((uintptr_t)g.ids & 15) == 0;
-  if (!quad || g.B != a.B || (a.C != 32 && a.C != 64 && a.C != 128)) {
+  const ArgmaxForm f = choose_post_seg(g.HW, (unsigned)((uintptr_t)g.seg & 15), (unsigned)((uintptr_t)g.ids & 15), a.B, g.B, a.C);
+  if (!f.fused) {
     if (int e = launch_post(a, s)) return e;
     return launch_seg_argmax(g, s);
   }
@@ -199,7 +204,7 @@ int launch_seg_sample_argmax(const SegSampleArgs& a, hipStream_t s) {
 }
 
 int launch_seg_argmax(const ArgmaxArgs& a, hipStream_t s) {
-  if ((a.HW & 3) == 0 && ((uintptr_t)a.seg & 15) == 0 && ((uintptr_t)a.ids & 15) == 0)
+  if (choose_argmax(a.HW, (unsigned)((uintptr_t)a.seg & 15), (unsigned)((uintptr_t)a.ids & 15)).quad)
     hipLaunchKernelGGL(seg_argmax4_kernel, dim3((a.HW / 4 + 255) / 256, a.B), dim3(256), 0, s, a);
   else
     hipLaunchKernelGGL(seg_argmax_kernel, dim3((a.HW + 255) / 256, a.B), dim3(256), 0, s, a);
@@ -211,17 +216,18 @@ int launch_seg_argmax(const ArgmaxArgs& a, hipStream_t s) {
 // they are unique: an 8-pass MSB radix select finds the count-th largest key exactly, the survivors
 // are compacted and sorted descending -> (score desc, index asc), deterministic.
 //   k <= TOPK_LDS_MAX: survivors live in LDS (8 B per key, up to 128 KiB of the CU's 160) and are bitonic-sorted there
-//                      (256 threads up to 4096 keys, 1024 beyond);
+//                      (256 threads up to KP2D_TOPK_SMALL keys, itself honoured up to 4096; 1024 beyond);
 //   larger k ("no cap": every cell above the threshold, frontend.py:122 / visual_odometry.py:112 with top_k <= 0, or
 //   a cap above 16384 on a big frame): survivors are compacted into the caller's idx row and sorted IN PLACE in
 //   global memory, keys rebuilt from score[idx] — no scratch buffer in the ABI, any k up to n.
 // ---------------------------------------------------------------------------------------------
-// (TOPK_SMALL_MAX, options.h: 256-thread workgroups up to there; beyond, 1024 threads hold one key each in the sort)
-constexpr int TOPK_LDS_MAX = 16384;      // keys that fit the LDS path
+// (TOPK_SMALL_MAX, options.h: 256-thread workgroups up to there; beyond, 1024 threads hold one key each in the sort.
+//  TOPK_LDS_MAX, TOPK_KPT and every choice of launch_topk: select_form.h)
 
 __device__ __forceinline__ unsigned long long topk_key(float s, int idx, float thr) {
   if (!(s > thr)) return 0ull;
   unsigned u = __float_as_uint(s);
+  if (u == 0x80000000u) u = 0u;      // -0.0 ranks as +0.0 (torch.topk, the reference's lexsort): index asc decides between them
   u = (u & 0x80000000u) ? ~u : (u | 0x80000000u);
   return ((unsigned long long)u << 32) | (unsigned long long)(0xFFFFFFFFu - (unsigned)idx);
 }
@@ -231,7 +237,6 @@ __device__ __forceinline__ unsigned long long topk_key(float s, int idx, float t
 // (1: every candidate, ~0: nothing) and the number of selected keys through `count_out`.
 // kreg / cached: the thread's keys (element tid + u NTHR) already in registers — the frame is then read from memory
 // once, all loads in flight together, instead of once per pass in a loop whose round trips run one after another
-constexpr int TOPK_KPT = 8;
 template <int NTHR>
 __device__ __forceinline__ unsigned long long topk_threshold(const float* sc, int n, int k, float thr, unsigned* hist,
                                                              unsigned long long& s_prefix, unsigned& count_out,
@@ -322,7 +327,7 @@ __global__ __launch_bounds__(NTHR) void topk_kernel(const TopkArgs a, const int 
 
   // kpow >= 2 always (launch_topk): the sort's first compare reads s_keys[0] and s_keys[1], both inside the key region
   for (int e = tid; e < kpow; e += NTHR) s_keys[e] = 0ull;
-  const bool cached = n <= TOPK_KPT * NTHR;
+  const bool cached = topk_cached(n, NTHR);
   unsigned long long kreg[TOPK_KPT];
 #pragma unroll
   for (int u = 0; u < TOPK_KPT; ++u) {
@@ -355,7 +360,7 @@ __global__ __launch_bounds__(NTHR) void topk_kernel(const TopkArgs a, const int 
   // bitonic sort, descending, of the smallest power-of-two prefix that holds the selected keys (the rest are zeros)
   int ksort = 2;
   while (ksort < (int)count) ksort <<= 1;
-  if (ksort <= NTHR) {
+  if (topk_register_sort(ksort, NTHR)) {
     // One key per thread, in a register.  Compare-exchanges whose partner is in the same wave (stride < 64: 45 of the
     // 55 steps at 1024 keys) are two lane shuffles; only the wider ones go through LDS, ping-ponging between the key
     // array and a second buffer so that each costs ONE barrier.  (A barrier per step, 1024 threads: 14 us of the
@@ -462,21 +467,22 @@ __global__ __launch_bounds__(1024) void topk_global_kernel(const TopkArgs a) {
 }
 
 int launch_topk(const TopkArgs& a, hipStream_t s) {
-  if (a.k < 1 || a.n < 1) return -1300;
-  const int keff = a.k < a.n ? a.k : a.n;      // more than n keys can never be selected
-  if (keff > TOPK_LDS_MAX) {
-    hipLaunchKernelGGL(topk_global_kernel, dim3(a.B), dim3(1024), 0, s, a);
-    return (int)hipGetLastError();
-  }
-  int kpow = 2;                                 // >= 2: the sort network always touches two key slots
-  while (kpow < keff) kpow <<= 1;
-  const size_t lds = (size_t)kpow * 8 + 16 + 260 * 4 + 1024 * 8;
-  if (keff <= tuning().topk_small) {
-    hipLaunchKernelGGL(topk_kernel<256>, dim3(a.B), dim3(256), lds, s, a, kpow);
-  } else {
-    static PerDeviceOnce lds_once;      // per device: a handle may live on any visible device
-    if (int e = lds_opt_in(lds_once, reinterpret_cast<const void*>(&topk_kernel<1024>))) return e;
-    hipLaunchKernelGGL(topk_kernel<1024>, dim3(a.B), dim3(1024), lds, s, a, kpow);
+  TopkForm f;
+  if (int e = choose_topk(a.n, a.k, tuning().topk_small, f)) return e;
+  switch (f.kernel) {
+    case TOPK_GLOBAL:
+      hipLaunchKernelGGL(topk_global_kernel, dim3(a.B), dim3(1024), 0, s, a);
+      break;
+    case TOPK_256:
+      hipLaunchKernelGGL(topk_kernel<256>, dim3(a.B), dim3(256), f.lds, s, a, f.kpow);
+      break;
+    default: {
+      if (f.lds_opt_in) {
+        static PerDeviceOnce lds_once;      // per device: a handle may live on any visible device
+        if (int e = lds_opt_in(lds_once, reinterpret_cast<const void*>(&topk_kernel<1024>))) return e;
+      }
+      hipLaunchKernelGGL(topk_kernel<1024>, dim3(a.B), dim3(1024), f.lds, s, a, f.kpow);
+    }
   }
   return (int)hipGetLastError();
 }
@@ -524,7 +530,7 @@ __global__ __launch_bounds__(512) void gather_lds_kernel(const GatherArgs a) {
   const int b = blockIdx.y, g = blockIdx.x, C = a.C, k = a.k, n = a.n, tid = threadIdx.x;
   const float* dp = a.desc + ((size_t)b * C + (size_t)g * CPG) * n;
   const int tot = CPG * n;
-  if ((n & 3) == 0) {
+  if (gather_vec_copy(n)) {
     for (int e = tid; e < tot >> 2; e += 512) reinterpret_cast<float4*>(s_d)[e] = reinterpret_cast<const float4*>(dp)[e];
   } else {
     for (int e = tid; e < tot; e += 512) s_d[e] = dp[e];
@@ -537,7 +543,7 @@ __global__ __launch_bounds__(512) void gather_lds_kernel(const GatherArgs a) {
 #pragma unroll
     for (int c = 0; c < CPG; ++c) v[c] = idx >= 0 ? s_d[c * n + idx] : 0.f;
     float* o = a.dsel + ((size_t)b * k + j) * C + g * CPG;
-    if (CPG % 4 == 0 && (C & 3) == 0) {
+    if (gather_vec_store(CPG, C)) {
 #pragma unroll
       for (int c = 0; c < CPG; c += 4) *reinterpret_cast<float4*>(o + c) = make_float4(v[c], v[c + 1], v[c + 2], v[c + 3]);
     } else {
@@ -552,31 +558,25 @@ __global__ __launch_bounds__(512) void gather_lds_kernel(const GatherArgs a) {
 }
 
 int launch_gather(const GatherArgs& a, hipStream_t s) {
-  if (a.C < 2) return -1310;      // (x, y ride on channels 0 and 1)
-  // LDS form: selections of at least an eighth of the cells, planes that fit 64 KB in groups of 8 / 4 / 2 channels, and
-  // enough frames to fill the chip with (frame, channel group) workgroups (one frame: 0.268 vs 0.265 ms with the direct form)
-  if (tuning().gather_lds && (long)a.k * 8 >= a.n && (a.C & 7) == 0 && (long)a.B * (a.C / 8) >= 128) {
-    const dim3 block(512);
-    if ((long)a.n * 8 * 4 <= 65536) {
-      hipLaunchKernelGGL(gather_lds_kernel<8>, dim3(a.C / 8, a.B), block, (size_t)a.n * 8 * 4, s, a);
-      return (int)hipGetLastError();
-    }
-    // Four planes per workgroup keep the 16-byte stores of a keypoint's row; past 64 KB that takes the opt-in to the
-    // CU's whole LDS (4800 cells at 240 x 320: 76.8 KB, two workgroups per CU).  Two planes per workgroup wrote 8 bytes
-    // per keypoint from sixteen workgroups per frame: 30 us at 64 frames.
-    if ((long)a.n * 4 * 4 <= 80 * 1024) {
-      static PerDeviceOnce lds_once;
-      if (int e = lds_opt_in(lds_once, reinterpret_cast<const void*>(&gather_lds_kernel<4>))) return e;
-      hipLaunchKernelGGL(gather_lds_kernel<4>, dim3(a.C / 4, a.B), block, (size_t)a.n * 4 * 4, s, a);
-      return (int)hipGetLastError();
-    }
-    if ((long)a.n * 2 * 4 <= 65536) {
-      hipLaunchKernelGGL(gather_lds_kernel<2>, dim3(a.C / 2, a.B), block, (size_t)a.n * 2 * 4, s, a);
-      return (int)hipGetLastError();
-    }
+  GatherForm f;
+  if (int e = choose_gather(a.B, a.C, a.n, a.k, tuning().gather_lds, f)) return e;
+  if (f.kernel == GATHER_DIRECT) {
+    const int K4 = (a.k + 3) >> 2;
+    hipLaunchKernelGGL(gather_kernel, dim3((K4 * a.C + 255) / 256, a.B), dim3(256), 0, s, a);
+    return (int)hipGetLastError();
   }
-  const int K4 = (a.k + 3) >> 2;
-  hipLaunchKernelGGL(gather_kernel, dim3((K4 * a.C + 255) / 256, a.B), dim3(256), 0, s, a);
+  const dim3 grid(a.C / f.planes, a.B), block(512);
+  switch (f.planes) {
+    case 8: hipLaunchKernelGGL(gather_lds_kernel<8>, grid, block, f.lds, s, a); break;
+    case 4: {
+      static PerDeviceOnce lds_once;
+      if (f.lds_opt_in)
+        if (int e = lds_opt_in(lds_once, reinterpret_cast<const void*>(&gather_lds_kernel<4>))) return e;
+      hipLaunchKernelGGL(gather_lds_kernel<4>, grid, block, f.lds, s, a);
+      break;
+    }
+    default: hipLaunchKernelGGL(gather_lds_kernel<2>, grid, block, f.lds, s, a); break;
+  }
   return (int)hipGetLastError();
 }
 
