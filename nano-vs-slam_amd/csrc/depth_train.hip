@@ -19,6 +19,7 @@
 
 #include "api_common.h"
 #include "device_guard.h"
+#include "train_common.h"
 
 using namespace kp2d;
 
@@ -60,8 +61,6 @@ DepthPlan depth_plan(void* scratch, int N, int64_t HW) {
   p.total = c.bytes();
   return p;
 }
-
-bool misaligned(const void* p, size_t a) { return (uintptr_t)p % a != 0; }
 
 // 1: valid; 0: ignored (gt <= 0); -1: stray (gt or the logit is not finite)
 __device__ __forceinline__ int pixel_kind(float z, float gt) {
@@ -234,9 +233,8 @@ int kp2d_depth_loss(const float* logits, const float* gt, int N, int64_t HW, dou
   if (const char* why = depth_shape_problem(N, HW, &code)) return fail(code, "depth_loss: %s (N %d, HW %lld)", why, N, (long long)HW);
   if (!(silog_weight >= 0.0 && silog_weight < INFINITY && huber_weight >= 0.0 && huber_weight < INFINITY))
     return fail(KP2D_ERR_ARG, "depth_loss: weights %g, %g must be finite and not negative", silog_weight, huber_weight);
-  if (!logits || !gt || !loss || !parts || !dlogits || !valid || !stray || !scratch) return fail(KP2D_ERR_ARG, "null argument");
-  if (misaligned(logits, 4) || misaligned(gt, 4) || misaligned(loss, 4) || misaligned(parts, 4) || misaligned(dlogits, 4) ||
-      misaligned(valid, 8) || misaligned(stray, 8) || misaligned(scratch, 16))
+  if (any_null(logits, gt, loss, parts, dlogits, valid, stray, scratch)) return fail(KP2D_ERR_ARG, "null argument");
+  if (any_misaligned4(logits, gt, loss, parts, dlogits) || misaligned(valid, 8) || misaligned(stray, 8) || misaligned(scratch, 16))
     return fail(KP2D_ERR_ARG, "depth_loss: misaligned argument");
   const DepthPlan p = depth_plan(scratch, N, HW);
   if (scratch_bytes < p.total) return fail(KP2D_ERR_ARG, "depth_loss scratch %zu B < required %zu B (kp2d_depth_loss_scratch_bytes)", scratch_bytes, p.total);

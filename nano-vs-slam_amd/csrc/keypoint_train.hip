@@ -30,6 +30,7 @@
 
 #include "api_common.h"
 #include "device_guard.h"
+#include "train_common.h"
 
 using namespace kp2d;
 
@@ -672,8 +673,6 @@ Geo make_geo(int B, int Hc, int Wc, int C, int Hf, int Wf, int H, int W, int cel
   g.relax = (float)relax;
   return g;
 }
-
-bool misaligned(const void* p, size_t a) { return (uintptr_t)p % a != 0; }
 
 }  // namespace
 

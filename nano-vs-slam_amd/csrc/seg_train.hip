@@ -45,17 +45,6 @@ BiasPlan bias_plan(void* scratch, int N, int H, int W, int Cin, int Cout) {
   return p;
 }
 
-const char* bias_shape_problem(int N, int H, int W, int Cin, int Cout, int* code) {
-  *code = KP2D_ERR_ARG;
-  if (N < 1 || N > 65535) return "N outside [1, 65535]";
-  if (H < 1 || W < 1) return "H and W must be at least 1";
-  if (Cin < 1 || Cout < 1) return "Cin and Cout must be at least 1";
-  *code = KP2D_ERR_UNSUPPORTED;
-  if (Cin % 16 || Cin < MIN_CH || Cin > MAX_CH || Cout > MAX_CH) return "needs Cin % 16 == 0, 16 <= Cin <= 128 and 1 <= Cout <= 128";
-  if ((int64_t)H * W > ((int64_t)1 << 30)) return "H * W above 2^30";
-  return nullptr;
-}
-
 // part[b CO + co] = the sum of one plane of dy: a thread's strided elements in order, the wave's 64, the four waves
 __global__ __launch_bounds__(256) void sb_plane_kernel(const float* __restrict__ dy, float* __restrict__ part, int CO, size_t HW) {
   __shared__ float s_r[4];
@@ -336,68 +325,44 @@ extern "C" {
 
 size_t kp2d_conv_bias_scratch_bytes(int N, int H, int W, int Cin, int Cout) {
   int code;
-  if (bias_shape_problem(N, H, W, Cin, Cout, &code)) return 0;
+  if (conv_shape_problem(N, H, W, Cin, Cout, false, &code)) return 0;
   return bias_plan(nullptr, N, H, W, Cin, Cout).total;
 }
 
 int kp2d_conv_bias_forward_train(const float* x, const float* w, const float* bias, int N, int H, int W, int Cin, int Cout, float* y,
                                  void* scratch, size_t scratch_bytes, void* stream) {
   int code;
-  if (const char* why = bias_shape_problem(N, H, W, Cin, Cout, &code))
+  if (const char* why = conv_shape_problem(N, H, W, Cin, Cout, false, &code))
     return fail(code, "conv_bias_forward_train: %s (N %d, H %d, W %d, Cin %d, Cout %d)", why, N, H, W, Cin, Cout);
-  if (!x || !w || !bias || !y || !scratch) return fail(KP2D_ERR_ARG, "null argument");
-  if (misaligned(x, 4) || misaligned(w, 4) || misaligned(bias, 4) || misaligned(y, 4) || misaligned(scratch, 16))
+  if (any_null(x, w, bias, y, scratch)) return fail(KP2D_ERR_ARG, "null argument");
+  if (any_misaligned4(x, w, bias, y) || misaligned(scratch, 16))
     return fail(KP2D_ERR_ARG, "conv_bias_forward_train: float arrays must be 4-byte aligned, scratch 16-byte");
   const BiasPlan p = bias_plan(scratch, N, H, W, Cin, Cout);
   if (scratch_bytes < p.total) return fail(KP2D_ERR_ARG, "conv_bias_forward_train scratch %zu B < required %zu B (kp2d_conv_bias_scratch_bytes)", scratch_bytes, p.total);
   hipStream_t st = (hipStream_t)stream;
   DeviceGuard guard(x, st);
-  const Geo g = geo_of(N, H, W);
-  const int CP = pad16(Cout);
-  hipLaunchKernelGGL(hc_pack_pad_kernel, dim3((CP * Cin * 9 + 255) / 256), dim3(256), 0, st, w, p.wp, Cout, Cin, 0);
-  HIP_TRY(hipGetLastError());
   ConvMA a{};
-  a.in = x; a.wp = p.wp; a.y_out = y; a.CI = Cin; a.H = H; a.W = W; a.tiles_x = g.tiles_x;
-  a.ci_real = Cin; a.co_real = Cout; a.bias = bias;
-  if (int e = launch_conv<true>(a, CP, N, g, st)) return fail(KP2D_ERR_HIP, "conv_bias_forward_train: conv kernel: %d", e);
-  return KP2D_OK;
+  a.y_out = y; a.bias = bias;
+  return conv_forward<true>({"conv_bias_forward_train", x, w, p.wp, N, H, W, Cin, Cout, st}, a);
 }
 
 int kp2d_conv_bias_backward(const float* x, const float* w, const float* dy, int N, int H, int W, int Cin, int Cout, float* d_weight,
                             float* d_bias, float* dx, void* scratch, size_t scratch_bytes, void* stream) {
   int code;
-  if (const char* why = bias_shape_problem(N, H, W, Cin, Cout, &code))
+  if (const char* why = conv_shape_problem(N, H, W, Cin, Cout, false, &code))
     return fail(code, "conv_bias_backward: %s (N %d, H %d, W %d, Cin %d, Cout %d)", why, N, H, W, Cin, Cout);
-  if (!x || !w || !dy || !d_weight || !d_bias || !scratch) return fail(KP2D_ERR_ARG, "null argument");
-  if (misaligned(x, 4) || misaligned(w, 4) || misaligned(dy, 4) || misaligned(d_weight, 4) || misaligned(d_bias, 4) || misaligned(dx, 4) ||
-      misaligned(scratch, 16))
+  if (any_null(x, w, dy, d_weight, d_bias, scratch)) return fail(KP2D_ERR_ARG, "null argument");
+  if (any_misaligned4(x, w, dy, d_weight, d_bias, dx) || misaligned(scratch, 16))
     return fail(KP2D_ERR_ARG, "conv_bias_backward: float arrays must be 4-byte aligned, scratch 16-byte");
   const BiasPlan p = bias_plan(scratch, N, H, W, Cin, Cout);
   if (scratch_bytes < p.total) return fail(KP2D_ERR_ARG, "conv_bias_backward scratch %zu B < required %zu B (kp2d_conv_bias_scratch_bytes)", scratch_bytes, p.total);
   hipStream_t st = (hipStream_t)stream;
   DeviceGuard guard(x, st);
-  const Geo g = geo_of(N, H, W);
-  const int CP = pad16(Cout);
   hipLaunchKernelGGL(sb_plane_kernel, dim3(Cout, N), dim3(256), 0, st, dy, p.bp, Cout, (size_t)H * W);
   HIP_TRY(hipGetLastError());
   hipLaunchKernelGGL(sb_sum_kernel, dim3(1), dim3(128), 0, st, p.bp, d_bias, N, Cout);
   HIP_TRY(hipGetLastError());
-  DwMA d{};
-  d.dc = dy; d.x = x; d.part = p.dwp; d.tiles = g.tiles; d.tps = g.tps; d.CI = Cin; d.H = H; d.W = W; d.tiles_x = g.tiles_x; d.tpf = g.tpf;
-  d.co_real = Cout;
-  if (int e = launch_dw<true>(d, CP, g, st)) return fail(KP2D_ERR_HIP, "conv_bias_backward: weight-gradient kernel: %d", e);
-  const int nw = Cout * Cin * 9;
-  hipLaunchKernelGGL(hc_dw_sum_kernel, dim3((nw + 255) / 256), dim3(256), 0, st, p.dwp, d_weight, g.slabs, nw);
-  HIP_TRY(hipGetLastError());
-  if (dx) {      // the forward kernel on dy: input channels Cout (padded, masked), output channels Cin
-    hipLaunchKernelGGL(hc_pack_pad_kernel, dim3((CP * Cin * 9 + 255) / 256), dim3(256), 0, st, w, p.wp, Cout, Cin, 1);
-    HIP_TRY(hipGetLastError());
-    ConvMA a{};
-    a.in = dy; a.wp = p.wp; a.y_out = dx; a.CI = CP; a.H = H; a.W = W; a.tiles_x = g.tiles_x;
-    a.ci_real = Cout; a.co_real = Cin;
-    if (int e = launch_conv<true>(a, Cin, N, g, st)) return fail(KP2D_ERR_HIP, "conv_bias_backward: data-gradient kernel: %d", e);
-  }
-  return KP2D_OK;
+  return conv_backward_tail<true>({"conv_bias_backward", x, w, p.wp, N, H, W, Cin, Cout, st}, dy, p.dwp, d_weight, dx);
 }
 
 static const char* loss_shape_problem(int N, int64_t HW, int C, int* code) {
@@ -426,9 +391,9 @@ int kp2d_seg_loss(const float* logits, const void* labels, int label_dtype, int 
     return fail(KP2D_ERR_ARG, "seg_loss: label_dtype = %d (KP2D_SEG_U8, KP2D_SEG_I32 or KP2D_SEG_I64)", label_dtype);
   if (!(ce_weight >= 0.0 && ce_weight < INFINITY && dice_weight >= 0.0 && dice_weight < INFINITY))
     return fail(KP2D_ERR_ARG, "seg_loss: weights %g, %g must be finite and not negative", ce_weight, dice_weight);
-  if (!logits || !labels || !loss || !dlogits || !valid || !stray || !scratch) return fail(KP2D_ERR_ARG, "null argument");
-  if (misaligned(logits, 4) || misaligned(loss, 4) || misaligned(dlogits, 4) || misaligned(valid, 8) || misaligned(stray, 8) ||
-      misaligned(scratch, 16) || (label_dtype == KP2D_SEG_I64 && misaligned(labels, 8)) || (label_dtype == KP2D_SEG_I32 && misaligned(labels, 4)))
+  if (any_null(logits, labels, loss, dlogits, valid, stray, scratch)) return fail(KP2D_ERR_ARG, "null argument");
+  if (any_misaligned4(logits, loss, dlogits) || misaligned(valid, 8) || misaligned(stray, 8) || misaligned(scratch, 16) ||
+      (label_dtype == KP2D_SEG_I64 && misaligned(labels, 8)) || (label_dtype == KP2D_SEG_I32 && misaligned(labels, 4)))
     return fail(KP2D_ERR_ARG, "seg_loss: misaligned argument");
   const LossPlan p = loss_plan(scratch, N, HW, C);
   if (scratch_bytes < p.total) return fail(KP2D_ERR_ARG, "seg_loss scratch %zu B < required %zu B (kp2d_seg_loss_scratch_bytes)", scratch_bytes, p.total);
@@ -461,8 +426,8 @@ int kp2d_maxpool2_forward_train(const float* x, int N, int C, int H, int W, floa
   int code;
   if (const char* why = plane_problem(N, C, H, W, &code)) return fail(code, "maxpool2_forward_train: %s (N %d, C %d, H %d, W %d)", why, N, C, H, W);
   if (H < 2 || W < 2) return fail(KP2D_ERR_ARG, "maxpool2_forward_train: H %d and W %d must be at least 2", H, W);
-  if (!x || !y) return fail(KP2D_ERR_ARG, "null argument");
-  if (misaligned(x, 4) || misaligned(y, 4)) return fail(KP2D_ERR_ARG, "maxpool2_forward_train: float arrays must be 4-byte aligned");
+  if (any_null(x, y)) return fail(KP2D_ERR_ARG, "null argument");
+  if (any_misaligned4(x, y)) return fail(KP2D_ERR_ARG, "maxpool2_forward_train: float arrays must be 4-byte aligned");
   hipStream_t st = (hipStream_t)stream;
   DeviceGuard guard(x, st);
   const long long planes = (long long)N * C;
@@ -475,8 +440,8 @@ int kp2d_maxpool2_backward(const float* x, const float* dy, int N, int C, int H,
   int code;
   if (const char* why = plane_problem(N, C, H, W, &code)) return fail(code, "maxpool2_backward: %s (N %d, C %d, H %d, W %d)", why, N, C, H, W);
   if (H < 2 || W < 2) return fail(KP2D_ERR_ARG, "maxpool2_backward: H %d and W %d must be at least 2", H, W);
-  if (!x || !dy || !dx) return fail(KP2D_ERR_ARG, "null argument");
-  if (misaligned(x, 4) || misaligned(dy, 4) || misaligned(dx, 4)) return fail(KP2D_ERR_ARG, "maxpool2_backward: float arrays must be 4-byte aligned");
+  if (any_null(x, dy, dx)) return fail(KP2D_ERR_ARG, "null argument");
+  if (any_misaligned4(x, dy, dx)) return fail(KP2D_ERR_ARG, "maxpool2_backward: float arrays must be 4-byte aligned");
   hipStream_t st = (hipStream_t)stream;
   DeviceGuard guard(x, st);
   const long long planes = (long long)N * C;
@@ -497,7 +462,7 @@ int kp2d_shuffle_cat_forward(const float* a, const float* b, int N, int C, int C
   int code;
   if (const char* why = shuffle_problem(N, C, Cb, h, w, &code)) return fail(code, "shuffle_cat_forward: %s (N %d, C %d, Cb %d, h %d, w %d)", why, N, C, Cb, h, w);
   if (!a || (!b && Cb > 0) || !out) return fail(KP2D_ERR_ARG, "null argument");
-  if (misaligned(a, 4) || misaligned(b, 4) || misaligned(out, 4)) return fail(KP2D_ERR_ARG, "shuffle_cat_forward: float arrays must be 4-byte aligned");
+  if (any_misaligned4(a, b, out)) return fail(KP2D_ERR_ARG, "shuffle_cat_forward: float arrays must be 4-byte aligned");
   hipStream_t st = (hipStream_t)stream;
   DeviceGuard guard(a, st);
   hipLaunchKernelGGL(sc_forward_kernel, dim3(blocks_of((long long)N * (C + Cb) * 4 * h * w)), dim3(256), 0, st, a, b, out, N, C, Cb, h, w);
@@ -508,8 +473,8 @@ int kp2d_shuffle_cat_forward(const float* a, const float* b, int N, int C, int C
 int kp2d_shuffle_cat_backward(const float* dout, int N, int C, int Cb, int h, int w, float* da, void* stream) {
   int code;
   if (const char* why = shuffle_problem(N, C, Cb, h, w, &code)) return fail(code, "shuffle_cat_backward: %s (N %d, C %d, Cb %d, h %d, w %d)", why, N, C, Cb, h, w);
-  if (!dout || !da) return fail(KP2D_ERR_ARG, "null argument");
-  if (misaligned(dout, 4) || misaligned(da, 4)) return fail(KP2D_ERR_ARG, "shuffle_cat_backward: float arrays must be 4-byte aligned");
+  if (any_null(dout, da)) return fail(KP2D_ERR_ARG, "null argument");
+  if (any_misaligned4(dout, da)) return fail(KP2D_ERR_ARG, "shuffle_cat_backward: float arrays must be 4-byte aligned");
   hipStream_t st = (hipStream_t)stream;
   DeviceGuard guard(dout, st);
   hipLaunchKernelGGL(sc_backward_kernel, dim3(blocks_of((long long)N * 4 * C * h * w)), dim3(256), 0, st, dout, da, N, C, Cb, h, w);

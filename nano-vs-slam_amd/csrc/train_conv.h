@@ -12,6 +12,8 @@
 // MASK = true (seg_train.hip's last layer) takes a channel count that is no multiple of 16 on w's Cout axis: the packed
 // weights are padded with zeros to the next multiple of 16 (hc_pack_pad_kernel), a padded channel is staged as exact zeros
 // without a load and is never stored; the epilogue adds a bias.  MASK = false is the kernel as it always was.
+// Host side, for the entry points of both files: conv_shape_problem (what N, H, W, Cin, Cout the kernels take), conv_forward
+// (pack the weights, convolve) and conv_backward_tail (weight gradient, and on request the data gradient).
 // Every kernel lives in an anonymous namespace: each translation unit that includes this header gets its own copies.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -289,7 +291,19 @@ inline Geo geo_of(int N, int H, int W) {
   return g;
 }
 
-inline bool misaligned(const void* p, size_t a) { return (uintptr_t)p % a != 0; }
+// why the kernels do not take these sizes (*code: the entry point's return value), or null.  cout16: a layer with a BatchNorm,
+// Cout a multiple of 16 in [16, 128]; otherwise the MASK form's any 1 <= Cout <= 128
+inline const char* conv_shape_problem(int N, int H, int W, int Cin, int Cout, bool cout16, int* code) {
+  *code = KP2D_ERR_ARG;
+  if (N < 1 || N > 65535) return "N outside [1, 65535]";
+  if (H < 1 || W < 1) return "H and W must be at least 1";
+  if (Cin < 1 || Cout < 1) return "Cin and Cout must be at least 1";
+  *code = KP2D_ERR_UNSUPPORTED;
+  if (Cin % 16 || Cin < MIN_CH || Cin > MAX_CH || Cout > MAX_CH || (cout16 && (Cout % 16 || Cout < MIN_CH)))
+    return cout16 ? "needs Cin % 16 == 0, Cout % 16 == 0 and 16 <= Cin, Cout <= 128" : "needs Cin % 16 == 0, 16 <= Cin <= 128 and 1 <= Cout <= 128";
+  if ((int64_t)H * W > ((int64_t)1 << 30)) return "H * W above 2^30";
+  return nullptr;
+}
 
 template <int NT, bool MASK>
 int launch_conv_t(const ConvArgs<MASK>& a, const dim3& grid, hipStream_t st) {
@@ -338,6 +352,60 @@ int launch_dw(const DwArgs<MASK>& a, int CO, const Geo& g, hipStream_t st) {
     case 8: return launch_dw_t<8, MASK>(a, grid, st);
   }
   return -1000;
+}
+
+// ---- the two halves of a conv-shaped entry point -----------------------------------------------------------------------
+struct ConvCall {
+  const char* who;      // the entry point's name in its messages
+  const float* x;       // [N][Cin][H][W]
+  const float* w;       // [Cout][Cin][3][3]
+  float* wp;            // scratch of 9 Cin Cout floats (MASK: Cout padded to 16) for the packed weights
+  int N, H, W, Cin, Cout;
+  hipStream_t st;
+};
+
+// w in the form hc_conv_kernel stages: dgrad 0 the forward's, 1 the data gradient's
+template <bool MASK>
+void launch_pack(const ConvCall& k, int dgrad) {
+  const dim3 grid(((MASK ? pad16(k.Cout) : k.Cout) * k.Cin * 9 + 255) / 256);
+  if constexpr (MASK) hipLaunchKernelGGL(hc_pack_pad_kernel, grid, dim3(256), 0, k.st, k.w, k.wp, k.Cout, k.Cin, dgrad);
+  else hipLaunchKernelGGL(hc_pack_kernel, grid, dim3(256), 0, k.st, k.w, k.wp, k.Cout, k.Cin, dgrad);
+}
+
+// pack, then convolve x.  `a` brings the epilogue (scale, shift, slope, c_out, y_out; MASK: bias); the rest is filled in here
+template <bool MASK>
+int conv_forward(const ConvCall& k, ConvArgs<MASK> a) {
+  const Geo g = geo_of(k.N, k.H, k.W);
+  launch_pack<MASK>(k, 0);
+  HIP_TRY(hipGetLastError());
+  a.in = k.x; a.wp = k.wp; a.CI = k.Cin; a.H = k.H; a.W = k.W; a.tiles_x = g.tiles_x;
+  if constexpr (MASK) { a.ci_real = k.Cin; a.co_real = k.Cout; }
+  if (int e = launch_conv<MASK>(a, MASK ? pad16(k.Cout) : k.Cout, k.N, g, k.st)) return fail(KP2D_ERR_HIP, "%s: conv kernel: %d", k.who, e);
+  return KP2D_OK;
+}
+
+// from dc [N][Cout][H][W], the gradient of the convolution's result: the weight gradient's partials per slab (dwp), their
+// ordered sum into d_weight, and with dx the forward kernel on dc (input channels Cout, MASK: padded and masked; output
+// channels Cin; the weights turned and swapped).  d_weight has the same bits with and without dx.
+template <bool MASK>
+int conv_backward_tail(const ConvCall& k, const float* dc, float* dwp, float* d_weight, float* dx) {
+  const Geo g = geo_of(k.N, k.H, k.W);
+  const int CP = MASK ? pad16(k.Cout) : k.Cout;
+  DwArgs<MASK> d{};
+  d.dc = dc; d.x = k.x; d.part = dwp; d.tiles = g.tiles; d.tps = g.tps; d.CI = k.Cin; d.H = k.H; d.W = k.W; d.tiles_x = g.tiles_x; d.tpf = g.tpf;
+  if constexpr (MASK) d.co_real = k.Cout;
+  if (int e = launch_dw<MASK>(d, CP, g, k.st)) return fail(KP2D_ERR_HIP, "%s: weight-gradient kernel: %d", k.who, e);
+  const int nw = k.Cout * k.Cin * 9;
+  hipLaunchKernelGGL(hc_dw_sum_kernel, dim3((nw + 255) / 256), dim3(256), 0, k.st, dwp, d_weight, g.slabs, nw);
+  HIP_TRY(hipGetLastError());
+  if (!dx) return KP2D_OK;
+  launch_pack<MASK>(k, 1);
+  HIP_TRY(hipGetLastError());
+  ConvArgs<MASK> a{};
+  a.in = dc; a.wp = k.wp; a.y_out = dx; a.CI = CP; a.H = k.H; a.W = k.W; a.tiles_x = g.tiles_x;
+  if constexpr (MASK) { a.ci_real = k.Cout; a.co_real = k.Cin; }
+  if (int e = launch_conv<MASK>(a, k.Cin, k.N, g, k.st)) return fail(KP2D_ERR_HIP, "%s: data-gradient kernel: %d", k.who, e);
+  return KP2D_OK;
 }
 
 }  // namespace

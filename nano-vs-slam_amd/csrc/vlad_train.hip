@@ -507,8 +507,6 @@ int launch_tile(const TileArgs& a, int N, hipStream_t st) {
   return (int)hipGetLastError();
 }
 
-bool misaligned(const void* p, size_t a) { return (uintptr_t)p % a != 0; }
-
 }  // namespace
 
 extern "C" {
@@ -523,8 +521,8 @@ int kp2d_vlad_forward_train(const float* x, const float* weight, const float* ce
                             float* vlad, float* saved, void* scratch, size_t scratch_bytes, void* stream) {
   int code;
   if (const char* why = shape_problem(N, S, C, K, &code)) return fail(code, "vlad_forward_train: %s (N %d, S %d, C %d, K %d)", why, N, S, C, K);
-  if (!x || !weight || !centroids || !vlad || !saved || !scratch) return fail(KP2D_ERR_ARG, "null argument");
-  if (misaligned(x, 4) || misaligned(weight, 4) || misaligned(centroids, 4) || misaligned(vlad, 4) || misaligned(saved, 4) || misaligned(scratch, 16))
+  if (any_null(x, weight, centroids, vlad, saved, scratch)) return fail(KP2D_ERR_ARG, "null argument");
+  if (any_misaligned4(x, weight, centroids, vlad, saved) || misaligned(scratch, 16))
     return fail(KP2D_ERR_ARG, "vlad_forward_train: float arrays must be 4-byte aligned, scratch 16-byte");
   const TrainPlan p = train_plan(scratch, N, S, C, K);
   if (scratch_bytes < p.total) return fail(KP2D_ERR_ARG, "vlad_forward_train scratch %zu B < required %zu B (kp2d_vlad_train_scratch_bytes)", scratch_bytes, p.total);
@@ -546,9 +544,8 @@ int kp2d_vlad_backward(const float* x, const float* weight, const float* centroi
                        void* stream) {
   int code;
   if (const char* why = shape_problem(N, S, C, K, &code)) return fail(code, "vlad_backward: %s (N %d, S %d, C %d, K %d)", why, N, S, C, K);
-  if (!x || !weight || !centroids || !saved || !dvlad || !d_weight || !d_centroids || !scratch) return fail(KP2D_ERR_ARG, "null argument");
-  if (misaligned(x, 4) || misaligned(weight, 4) || misaligned(centroids, 4) || misaligned(saved, 4) || misaligned(dvlad, 4) ||
-      misaligned(d_weight, 4) || misaligned(d_centroids, 4) || misaligned(scratch, 16))
+  if (any_null(x, weight, centroids, saved, dvlad, d_weight, d_centroids, scratch)) return fail(KP2D_ERR_ARG, "null argument");
+  if (any_misaligned4(x, weight, centroids, saved, dvlad, d_weight, d_centroids) || misaligned(scratch, 16))
     return fail(KP2D_ERR_ARG, "vlad_backward: float arrays must be 4-byte aligned, scratch 16-byte");
   const TrainPlan p = train_plan(scratch, N, S, C, K);
   if (scratch_bytes < p.total) return fail(KP2D_ERR_ARG, "vlad_backward scratch %zu B < required %zu B (kp2d_vlad_train_scratch_bytes)", scratch_bytes, p.total);
@@ -575,9 +572,8 @@ int kp2d_vlad_backward_input(const float* x, const float* weight, const float* c
   if (const char* why = shape_problem(N, S, C, K, &code)) return fail(code, "vlad_backward_input: %s (N %d, S %d, C %d, K %d)", why, N, S, C, K);
   if (C > DX_MAX_C || tile_lds_floats_dx(K, C) * sizeof(float) > (size_t)LDS_BUDGET)
     return fail(KP2D_ERR_UNSUPPORTED, "vlad_backward_input: needs C <= %d and a tile within 160 KB of LDS (C %d, K %d)", DX_MAX_C, C, K);
-  if (!x || !weight || !centroids || !saved || !dvlad || !dx || !scratch) return fail(KP2D_ERR_ARG, "null argument");
-  if (misaligned(x, 4) || misaligned(weight, 4) || misaligned(centroids, 4) || misaligned(saved, 4) || misaligned(dvlad, 4) ||
-      misaligned(dx, 4) || misaligned(scratch, 16))
+  if (any_null(x, weight, centroids, saved, dvlad, dx, scratch)) return fail(KP2D_ERR_ARG, "null argument");
+  if (any_misaligned4(x, weight, centroids, saved, dvlad, dx) || misaligned(scratch, 16))
     return fail(KP2D_ERR_ARG, "vlad_backward_input: float arrays must be 4-byte aligned, scratch 16-byte");
   const TrainPlan p = train_plan(scratch, N, S, C, K);
   if (scratch_bytes < p.total) return fail(KP2D_ERR_ARG, "vlad_backward_input scratch %zu B < required %zu B (kp2d_vlad_train_scratch_bytes)", scratch_bytes, p.total);
@@ -598,8 +594,8 @@ int kp2d_triplet_loss(const float* vlad, int B, const int32_t* neg_offset, int n
   if (B < 1 || n_neg < 0 || dim < 1) return fail(KP2D_ERR_ARG, "triplet_loss: B %d, n_neg %d, dim %d", B, n_neg, dim);
   if ((int64_t)2 * B + n_neg > 65535) return fail(KP2D_ERR_UNSUPPORTED, "triplet_loss: more than 65535 descriptor rows");
   if (!(margin >= 0.0) || std::isinf(margin)) return fail(KP2D_ERR_ARG, "triplet_loss: margin %g", margin);
-  if (!vlad || !neg_offset || !loss || !dvlad || !n_active || !scratch) return fail(KP2D_ERR_ARG, "null argument");
-  if (misaligned(vlad, 4) || misaligned(neg_offset, 4) || misaligned(loss, 4) || misaligned(dvlad, 4) || misaligned(n_active, 4) || misaligned(scratch, 4))
+  if (any_null(vlad, neg_offset, loss, dvlad, n_active, scratch)) return fail(KP2D_ERR_ARG, "null argument");
+  if (any_misaligned4(vlad, neg_offset, loss, dvlad, n_active, scratch))
     return fail(KP2D_ERR_ARG, "triplet_loss: arrays must be 4-byte aligned");
   const int N = 2 * B + n_neg;
   const size_t need = (size_t)(B + n_neg) * sizeof(float);
@@ -628,8 +624,8 @@ int kp2d_adam_step(float* param, const float* grad, float* m, float* v, int64_t 
     return fail(KP2D_ERR_ARG, "adam_step: lr %g, betas (%g, %g), eps %g", lr, beta1, beta2, eps);
   if (n == 0) return KP2D_OK;
   if (n > (int64_t)INT32_MAX * 256) return fail(KP2D_ERR_UNSUPPORTED, "adam_step: more than 2^39 elements");
-  if (!param || !grad || !m || !v) return fail(KP2D_ERR_ARG, "null argument");
-  if (misaligned(param, 4) || misaligned(grad, 4) || misaligned(m, 4) || misaligned(v, 4)) return fail(KP2D_ERR_ARG, "adam_step: arrays must be 4-byte aligned");
+  if (any_null(param, grad, m, v)) return fail(KP2D_ERR_ARG, "null argument");
+  if (any_misaligned4(param, grad, m, v)) return fail(KP2D_ERR_ARG, "adam_step: arrays must be 4-byte aligned");
   // the two bias corrections in double, as torch forms them on the host
   const double bc1 = 1.0 - std::pow(beta1, (double)step);
   const double bc2 = 1.0 - std::pow(beta2, (double)step);

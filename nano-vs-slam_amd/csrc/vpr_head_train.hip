@@ -101,18 +101,6 @@ HeadPlan head_plan(void* scratch, int N, int H, int W, int Cin, int Cout) {
   return p;
 }
 
-const char* shape_problem(int N, int H, int W, int Cin, int Cout, int* code) {
-  *code = KP2D_ERR_ARG;
-  if (N < 1 || N > 65535) return "N outside [1, 65535]";
-  if (H < 1 || W < 1) return "H and W must be at least 1";
-  if (Cin < 1 || Cout < 1) return "Cin and Cout must be at least 1";
-  *code = KP2D_ERR_UNSUPPORTED;
-  if (Cin % 16 || Cout % 16 || Cin < MIN_CH || Cin > MAX_CH || Cout < MIN_CH || Cout > MAX_CH)
-    return "needs Cin % 16 == 0, Cout % 16 == 0 and 16 <= Cin, Cout <= 128";
-  if ((int64_t)H * W > ((int64_t)1 << 30)) return "H * W above 2^30";
-  return nullptr;
-}
-
 bool bad_slope(double s) { return !(s >= 0.0 && s < 1.0); }
 
 // ---- BatchNorm on the batch's own statistics, Dropout2d ---------------------------------------------------------------
@@ -247,71 +235,48 @@ extern "C" {
 
 size_t kp2d_cbr_train_scratch_bytes(int N, int H, int W, int Cin, int Cout) {
   int code;
-  if (shape_problem(N, H, W, Cin, Cout, &code)) return 0;
+  if (conv_shape_problem(N, H, W, Cin, Cout, true, &code)) return 0;
   return head_plan(nullptr, N, H, W, Cin, Cout).total;
 }
 
 int kp2d_cbr_forward_train(const float* x, const float* w, const float* scale, const float* shift, double slope, int N, int H,
                            int W, int Cin, int Cout, float* y, float* c, void* scratch, size_t scratch_bytes, void* stream) {
   int code;
-  if (const char* why = shape_problem(N, H, W, Cin, Cout, &code))
+  if (const char* why = conv_shape_problem(N, H, W, Cin, Cout, true, &code))
     return fail(code, "cbr_forward_train: %s (N %d, H %d, W %d, Cin %d, Cout %d)", why, N, H, W, Cin, Cout);
   if (bad_slope(slope)) return fail(KP2D_ERR_ARG, "cbr_forward_train: slope %g outside [0, 1)", slope);
-  if (!x || !w || !scale || !shift || !y || !c || !scratch) return fail(KP2D_ERR_ARG, "null argument");
-  if (misaligned(x, 4) || misaligned(w, 4) || misaligned(scale, 4) || misaligned(shift, 4) || misaligned(y, 4) || misaligned(c, 4) ||
-      misaligned(scratch, 16))
+  if (any_null(x, w, scale, shift, y, c, scratch)) return fail(KP2D_ERR_ARG, "null argument");
+  if (any_misaligned4(x, w, scale, shift, y, c) || misaligned(scratch, 16))
     return fail(KP2D_ERR_ARG, "cbr_forward_train: float arrays must be 4-byte aligned, scratch 16-byte");
   const HeadPlan p = head_plan(scratch, N, H, W, Cin, Cout);
   if (scratch_bytes < p.total) return fail(KP2D_ERR_ARG, "cbr_forward_train scratch %zu B < required %zu B (kp2d_cbr_train_scratch_bytes)", scratch_bytes, p.total);
   hipStream_t st = (hipStream_t)stream;
   DeviceGuard guard(x, st);
-  const Geo g = geo_of(N, H, W);
-  hipLaunchKernelGGL(hc_pack_kernel, dim3((Cout * Cin * 9 + 255) / 256), dim3(256), 0, st, w, p.wp, Cout, Cin, 0);
-  HIP_TRY(hipGetLastError());
   ConvA a{};
-  a.in = x; a.wp = p.wp; a.scale = scale; a.shift = shift; a.c_out = c; a.y_out = y;
-  a.CI = Cin; a.H = H; a.W = W; a.tiles_x = g.tiles_x; a.slope = (float)slope;
-  if (int e = launch_conv<false>(a, Cout, N, g, st)) return fail(KP2D_ERR_HIP, "cbr_forward_train: conv kernel: %d", e);
-  return KP2D_OK;
+  a.scale = scale; a.shift = shift; a.c_out = c; a.y_out = y; a.slope = (float)slope;
+  return conv_forward<false>({"cbr_forward_train", x, w, p.wp, N, H, W, Cin, Cout, st}, a);
 }
 
 int kp2d_cbr_backward(const float* x, const float* w, const float* scale, const float* mean, const float* invstd, double slope,
                       const float* y, const float* c, const float* dy, int N, int H, int W, int Cin, int Cout, float* d_weight,
                       float* d_gamma, float* d_beta, float* dx, void* scratch, size_t scratch_bytes, void* stream) {
   int code;
-  if (const char* why = shape_problem(N, H, W, Cin, Cout, &code))
+  if (const char* why = conv_shape_problem(N, H, W, Cin, Cout, true, &code))
     return fail(code, "cbr_backward: %s (N %d, H %d, W %d, Cin %d, Cout %d)", why, N, H, W, Cin, Cout);
   if (bad_slope(slope)) return fail(KP2D_ERR_ARG, "cbr_backward: slope %g outside [0, 1)", slope);
-  if (!x || !w || !scale || !mean || !invstd || !y || !c || !dy || !d_weight || !d_gamma || !d_beta || !scratch)
-    return fail(KP2D_ERR_ARG, "null argument");
-  if (misaligned(x, 4) || misaligned(w, 4) || misaligned(scale, 4) || misaligned(mean, 4) || misaligned(invstd, 4) || misaligned(y, 4) ||
-      misaligned(c, 4) || misaligned(dy, 4) || misaligned(d_weight, 4) || misaligned(d_gamma, 4) || misaligned(d_beta, 4) ||
-      misaligned(dx, 4) || misaligned(scratch, 16))
+  if (any_null(x, w, scale, mean, invstd, y, c, dy, d_weight, d_gamma, d_beta, scratch)) return fail(KP2D_ERR_ARG, "null argument");
+  if (any_misaligned4(x, w, scale, mean, invstd, y, c, dy, d_weight, d_gamma, d_beta, dx) || misaligned(scratch, 16))
     return fail(KP2D_ERR_ARG, "cbr_backward: float arrays must be 4-byte aligned, scratch 16-byte");
   const HeadPlan p = head_plan(scratch, N, H, W, Cin, Cout);
   if (scratch_bytes < p.total) return fail(KP2D_ERR_ARG, "cbr_backward scratch %zu B < required %zu B (kp2d_cbr_train_scratch_bytes)", scratch_bytes, p.total);
   hipStream_t st = (hipStream_t)stream;
   DeviceGuard guard(x, st);
-  const Geo g = geo_of(N, H, W);
   const size_t HW = (size_t)H * W;
   hipLaunchKernelGGL(hc_dpre_kernel, dim3(Cout, N), dim3(256), 0, st, dy, y, c, scale, mean, invstd, (float)slope, p.dc, p.bn, Cout, HW);
   HIP_TRY(hipGetLastError());
   hipLaunchKernelGGL(hc_bn_sum_kernel, dim3(1), dim3(128), 0, st, p.bn, d_gamma, d_beta, N, Cout);
   HIP_TRY(hipGetLastError());
-  DwA d{};
-  d.dc = p.dc; d.x = x; d.part = p.dwp; d.tiles = g.tiles; d.tps = g.tps; d.CI = Cin; d.H = H; d.W = W; d.tiles_x = g.tiles_x; d.tpf = g.tpf;
-  if (int e = launch_dw<false>(d, Cout, g, st)) return fail(KP2D_ERR_HIP, "cbr_backward: weight-gradient kernel: %d", e);
-  const int nw = Cout * Cin * 9;
-  hipLaunchKernelGGL(hc_dw_sum_kernel, dim3((nw + 255) / 256), dim3(256), 0, st, p.dwp, d_weight, g.slabs, nw);
-  HIP_TRY(hipGetLastError());
-  if (dx) {      // the forward kernel on dc: input channels Cout, output channels Cin, weights turned and swapped
-    hipLaunchKernelGGL(hc_pack_kernel, dim3((nw + 255) / 256), dim3(256), 0, st, w, p.wp, Cout, Cin, 1);
-    HIP_TRY(hipGetLastError());
-    ConvA a{};
-    a.in = p.dc; a.wp = p.wp; a.y_out = dx; a.CI = Cout; a.H = H; a.W = W; a.tiles_x = g.tiles_x;
-    if (int e = launch_conv<false>(a, Cin, N, g, st)) return fail(KP2D_ERR_HIP, "cbr_backward: data-gradient kernel: %d", e);
-  }
-  return KP2D_OK;
+  return conv_backward_tail<false>({"cbr_backward", x, w, p.wp, N, H, W, Cin, Cout, st}, p.dc, p.dwp, d_weight, dx);
 }
 
 int kp2d_cbr_forward_batchnorm(const float* x, const float* w, const float* gamma, const float* beta, double eps, double slope,
@@ -319,29 +284,24 @@ int kp2d_cbr_forward_batchnorm(const float* x, const float* w, const float* gamm
                                int Cin, int Cout, float* y, float* c, float* mean, float* invstd, void* scratch,
                                size_t scratch_bytes, void* stream) {
   int code;
-  if (const char* why = shape_problem(N, H, W, Cin, Cout, &code))
+  if (const char* why = conv_shape_problem(N, H, W, Cin, Cout, true, &code))
     return fail(code, "cbr_forward_batchnorm: %s (N %d, H %d, W %d, Cin %d, Cout %d)", why, N, H, W, Cin, Cout);
   const double M = (double)N * H * W;
   if (M < 2.0) return fail(KP2D_ERR_ARG, "cbr_forward_batchnorm: batch statistics need N * H * W >= 2 values per channel, got %g", M);
   if (bad_slope(slope)) return fail(KP2D_ERR_ARG, "cbr_forward_batchnorm: slope %g outside [0, 1)", slope);
   if (!(eps >= 0.0 && eps < INFINITY)) return fail(KP2D_ERR_ARG, "cbr_forward_batchnorm: eps %g must be finite and not negative", eps);
   if (!(momentum >= 0.0 && momentum <= 1.0)) return fail(KP2D_ERR_ARG, "cbr_forward_batchnorm: momentum %g outside [0, 1]", momentum);
-  if (!x || !w || !gamma || !beta || !y || !c || !mean || !invstd || !scratch) return fail(KP2D_ERR_ARG, "null argument");
-  if (misaligned(x, 4) || misaligned(w, 4) || misaligned(gamma, 4) || misaligned(beta, 4) || misaligned(drop, 4) ||
-      misaligned(running_mean, 4) || misaligned(running_var, 4) || misaligned(y, 4) || misaligned(c, 4) || misaligned(mean, 4) ||
-      misaligned(invstd, 4) || misaligned(scratch, 16))
+  if (any_null(x, w, gamma, beta, y, c, mean, invstd, scratch)) return fail(KP2D_ERR_ARG, "null argument");
+  if (any_misaligned4(x, w, gamma, beta, drop, running_mean, running_var, y, c, mean, invstd) || misaligned(scratch, 16))
     return fail(KP2D_ERR_ARG, "cbr_forward_batchnorm: float arrays must be 4-byte aligned, scratch 16-byte");
   const HeadPlan p = head_plan(scratch, N, H, W, Cin, Cout);
   if (scratch_bytes < p.total) return fail(KP2D_ERR_ARG, "cbr_forward_batchnorm scratch %zu B < required %zu B (kp2d_cbr_train_scratch_bytes)", scratch_bytes, p.total);
   hipStream_t st = (hipStream_t)stream;
   DeviceGuard guard(x, st);
-  const Geo g = geo_of(N, H, W);
   const size_t HW = (size_t)H * W;
-  hipLaunchKernelGGL(hc_pack_kernel, dim3((Cout * Cin * 9 + 255) / 256), dim3(256), 0, st, w, p.wp, Cout, Cin, 0);
-  HIP_TRY(hipGetLastError());
   ConvA a{};      // the plain result, no affine
-  a.in = x; a.wp = p.wp; a.y_out = c; a.CI = Cin; a.H = H; a.W = W; a.tiles_x = g.tiles_x;
-  if (int e = launch_conv<false>(a, Cout, N, g, st)) return fail(KP2D_ERR_HIP, "cbr_forward_batchnorm: conv kernel: %d", e);
+  a.y_out = c;
+  if (int e = conv_forward<false>({"cbr_forward_batchnorm", x, w, p.wp, N, H, W, Cin, Cout, st}, a)) return e;
   hipLaunchKernelGGL(hb_plane_kernel, dim3(Cout, N), dim3(256), 0, st, c, p.bn, Cout, HW);
   HIP_TRY(hipGetLastError());
   hipLaunchKernelGGL(hb_stats_kernel, dim3(1), dim3(128), 0, st, p.bn, mean, invstd, running_mean, running_var, N, Cout, (float)HW,
@@ -357,22 +317,18 @@ int kp2d_cbr_backward_batchnorm(const float* x, const float* w, const float* gam
                                 int W, int Cin, int Cout, float* d_weight, float* d_gamma, float* d_beta, float* dx, void* scratch,
                                 size_t scratch_bytes, void* stream) {
   int code;
-  if (const char* why = shape_problem(N, H, W, Cin, Cout, &code))
+  if (const char* why = conv_shape_problem(N, H, W, Cin, Cout, true, &code))
     return fail(code, "cbr_backward_batchnorm: %s (N %d, H %d, W %d, Cin %d, Cout %d)", why, N, H, W, Cin, Cout);
   const double M = (double)N * H * W;
   if (M < 2.0) return fail(KP2D_ERR_ARG, "cbr_backward_batchnorm: batch statistics need N * H * W >= 2 values per channel, got %g", M);
   if (bad_slope(slope)) return fail(KP2D_ERR_ARG, "cbr_backward_batchnorm: slope %g outside [0, 1)", slope);
-  if (!x || !w || !gamma || !mean || !invstd || !y || !c || !dy || !d_weight || !d_gamma || !d_beta || !scratch)
-    return fail(KP2D_ERR_ARG, "null argument");
-  if (misaligned(x, 4) || misaligned(w, 4) || misaligned(gamma, 4) || misaligned(mean, 4) || misaligned(invstd, 4) || misaligned(drop, 4) ||
-      misaligned(y, 4) || misaligned(c, 4) || misaligned(dy, 4) || misaligned(d_weight, 4) || misaligned(d_gamma, 4) ||
-      misaligned(d_beta, 4) || misaligned(dx, 4) || misaligned(scratch, 16))
+  if (any_null(x, w, gamma, mean, invstd, y, c, dy, d_weight, d_gamma, d_beta, scratch)) return fail(KP2D_ERR_ARG, "null argument");
+  if (any_misaligned4(x, w, gamma, mean, invstd, drop, y, c, dy, d_weight, d_gamma, d_beta, dx) || misaligned(scratch, 16))
     return fail(KP2D_ERR_ARG, "cbr_backward_batchnorm: float arrays must be 4-byte aligned, scratch 16-byte");
   const HeadPlan p = head_plan(scratch, N, H, W, Cin, Cout);
   if (scratch_bytes < p.total) return fail(KP2D_ERR_ARG, "cbr_backward_batchnorm scratch %zu B < required %zu B (kp2d_cbr_train_scratch_bytes)", scratch_bytes, p.total);
   hipStream_t st = (hipStream_t)stream;
   DeviceGuard guard(x, st);
-  const Geo g = geo_of(N, H, W);
   const size_t HW = (size_t)H * W;
   hipLaunchKernelGGL(hb_dsum_kernel, dim3(Cout, N), dim3(256), 0, st, dy, y, c, mean, invstd, drop, (float)slope, p.bn, Cout, HW);
   HIP_TRY(hipGetLastError());
@@ -381,20 +337,7 @@ int kp2d_cbr_backward_batchnorm(const float* x, const float* w, const float* gam
   hipLaunchKernelGGL(hb_dc_kernel, dim3(Cout, N), dim3(256), 0, st, dy, y, c, gamma, mean, invstd, drop, d_gamma, d_beta, (float)slope,
                      (float)(1.0 / M), p.dc, Cout, HW);
   HIP_TRY(hipGetLastError());
-  DwA d{};
-  d.dc = p.dc; d.x = x; d.part = p.dwp; d.tiles = g.tiles; d.tps = g.tps; d.CI = Cin; d.H = H; d.W = W; d.tiles_x = g.tiles_x; d.tpf = g.tpf;
-  if (int e = launch_dw<false>(d, Cout, g, st)) return fail(KP2D_ERR_HIP, "cbr_backward_batchnorm: weight-gradient kernel: %d", e);
-  const int nw = Cout * Cin * 9;
-  hipLaunchKernelGGL(hc_dw_sum_kernel, dim3((nw + 255) / 256), dim3(256), 0, st, p.dwp, d_weight, g.slabs, nw);
-  HIP_TRY(hipGetLastError());
-  if (dx) {
-    hipLaunchKernelGGL(hc_pack_kernel, dim3((nw + 255) / 256), dim3(256), 0, st, w, p.wp, Cout, Cin, 1);
-    HIP_TRY(hipGetLastError());
-    ConvA a{};
-    a.in = p.dc; a.wp = p.wp; a.y_out = dx; a.CI = Cout; a.H = H; a.W = W; a.tiles_x = g.tiles_x;
-    if (int e = launch_conv<false>(a, Cin, N, g, st)) return fail(KP2D_ERR_HIP, "cbr_backward_batchnorm: data-gradient kernel: %d", e);
-  }
-  return KP2D_OK;
+  return conv_backward_tail<false>({"cbr_backward_batchnorm", x, w, p.wp, N, H, W, Cin, Cout, st}, p.dc, p.dwp, d_weight, dx);
 }
 
 int kp2d_dropout2d_mask(float* drop, int N, int C, double p, uint64_t seed, int64_t step, int layer, void* stream) {

@@ -6,7 +6,8 @@ and csrc/vpr_head_train.hip (include/kp2d.h).
 * ``depth_loss`` — ``silog_weight * SILogLoss + huber_weight * HuberLoss`` over the pixels with ``gt > 0``, taken from the
   logits before the sigmoid, with its gradient.
 * ``DepthHeadTrainer`` — forward, loss, backward and Adam for the head's 26 tensors (``train="head"``) or for the last layer's
-  two (``train="last"``); the walk over the nine layers is ``seg_training``'s, shared with ``SegHeadTrainer``.
+  two (``train="last"``); the walk over the nine layers is ``seg_training``'s, shared with ``SegHeadTrainer``; the layer calls
+  and the Adam core under it live in ``train_ops``.
 
 Conventions kept from the reference: SILog's constants 10 and 0.15 and torch's unbiased variance, Huber's delta 1 and mean
 reduction, ``huber_loss_factor`` 1.0, the mask ``gt > 0``, ``torch.optim.Adam``'s update, the parameters' registration order,
@@ -24,13 +25,14 @@ from __future__ import annotations
 
 import torch
 
-from . import _dev, _lib, seg_training as _st
+from . import _dev, _lib, train_ops as _ops
 from ._dev import ptr as _ptr, stream as _stream
+from .seg_training import _DenseHeadTrainer
 
 
 def _check_gt(where, gt, shape, device):
     """The ground truth as a float32 device tensor of the logits' [N, Hs, Ws] (or [N, 1, Hs, Ws]) -> [N, Hs, Ws]."""
-    if not isinstance(gt, torch.Tensor) or not _st._is_device(gt):
+    if not isinstance(gt, torch.Tensor) or not _ops._is_device(gt):
         raise ValueError(f"{where}: depth_gt must be a device tensor (there is no CPU path)")
     if gt.dtype != torch.float32:
         raise ValueError(f"{where}: depth_gt must be float32, got {gt.dtype}")
@@ -49,7 +51,7 @@ def depth_loss(logits, gt, silog_weight=1.0, huber_weight=1.0, scratch=None, ret
     valid pixels and of stray ones (gt or logit not finite: treated as invalid).  ``return_parts=True`` appends the float32
     device tensor [SILog, Huber], unweighted.  No valid pixel: loss 0, gradient 0."""
     where = "depth_loss"
-    if not isinstance(logits, torch.Tensor) or not _st._is_device(logits):
+    if not isinstance(logits, torch.Tensor) or not _ops._is_device(logits):
         raise ValueError(f"{where}: logits must be a device tensor (there is no CPU path)")
     if logits.dtype != torch.float32 or not (logits.dim() == 3 or (logits.dim() == 4 and logits.shape[1] == 1)):
         raise ValueError(f"{where}: logits must be float32 [N, 1, H, W] or [N, H, W], got {logits.dtype} {tuple(logits.shape)}")
@@ -84,7 +86,7 @@ def _no_depth_head(model):
     return "DepthHeadTrainer: the model was built without depth=True: it has no depth_head"
 
 
-class DepthHeadTrainer(_st._DenseHeadTrainer):
+class DepthHeadTrainer(_DenseHeadTrainer):
     """Adam on ``model.depth_head`` under the reference's depth loss, on a frozen backbone.
 
         trainer = DepthHeadTrainer(model, lr=1e-4, train="head", silog_weight=1.0, huber_weight=1.0)

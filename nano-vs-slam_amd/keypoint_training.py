@@ -7,7 +7,7 @@ kernels of csrc/keypoint_train.hip, csrc/seg_train.hip and csrc/vpr_head_train.h
   homography-warped view (the SOURCE view, ``out_aug``): location, descriptor triplet, USP and score consistency, with its
   gradient with respect to the six maps.
 * ``KeypointHeadTrainer`` — forward, loss, backward and Adam for any subset of the three heads, 5 + 5 + 10 tensors in the
-  reference's registration order; the layers are ``cbr_forward`` / ``cbr_backward``, ``conv_bias_forward`` /
+  reference's registration order; the layers are ``train_ops``'s ``cbr_forward`` / ``cbr_backward``, ``conv_bias_forward`` /
   ``conv_bias_backward``, ``shuffle_cat_forward`` / ``shuffle_cat_backward`` and ``adam_step``, as they are.
 * ``normalized_homography`` — a pixel homography as the loss takes it.
 
@@ -30,11 +30,11 @@ from __future__ import annotations
 
 import torch
 
-from . import _dev, _lib, seg_training as _st
+from . import _dev, _lib, train_ops as _ops
 from ._dev import ptr as _ptr, stream as _stream
-from .seg_training import conv_bias_backward, conv_bias_forward, shuffle_cat_backward, shuffle_cat_forward
-from .vlad_training import adam_step
-from .vpr_head_training import LEAKY_SLOPE, MAX_CH, MIN_CH, bn_vectors, cbr_backward, cbr_forward
+from .train_ops import (LEAKY_SLOPE, MAX_CH, MIN_CH, AdamTrainer, adam_step, bn_vectors, cbr_backward, cbr_forward,  # noqa: F401
+                        cbr_layer_backward, cbr_layer_forward, conv_bias_backward, conv_bias_forward, shuffle_cat_backward,
+                        shuffle_cat_forward)
 
 HEADS = ("score", "loc", "desc")
 MAX_CELLS, MIN_FEAT, MAX_FEAT = 65536, 16, 256
@@ -59,7 +59,7 @@ def _check_views(where, out, out_aug, homography):
             if not isinstance(d, dict) or key not in d or not isinstance(d[key], torch.Tensor):
                 raise ValueError(f"{where}: {view} must be a dict with the tensors 'score', 'coord' and 'feat' (the model's training forward)")
             maps.append((f"{view}['{key}']", d[key]))
-    _st._f32_maps(where, tuple(maps))
+    _ops._f32_maps(where, tuple(maps))
     score, shift, feat = out["score"], out["coord"], out["feat"]
     B, _, Hc, Wc = score.shape
     C, Hf, Wf = feat.shape[1:]
@@ -72,7 +72,7 @@ def _check_views(where, out, out_aug, homography):
 
 
 def _check_homography(where, homography, B, device):
-    if not isinstance(homography, torch.Tensor) or not _st._is_device(homography):
+    if not isinstance(homography, torch.Tensor) or not _ops._is_device(homography):
         raise ValueError(f"{where}: homography must be a device tensor (there is no CPU path)")
     if homography.dtype != torch.float32 or tuple(homography.shape) != (B, 3, 3):
         raise ValueError(f"{where}: homography must be float32 [{B}, 3, 3] in normalised coordinates, source to target "
@@ -162,7 +162,7 @@ def _check_model(model, train):
     return tuple(h for h in HEADS if h in train)
 
 
-class KeypointHeadTrainer:
+class KeypointHeadTrainer(AdamTrainer):
     """Adam on ``model.score_head``, ``model.loc_head`` and ``model.desc_head`` under the reference's keypoint loss, on a
     frozen backbone.
 
@@ -182,19 +182,18 @@ class KeypointHeadTrainer:
     models, a chosen head whose channel counts the conv kernels do not take (config N's 72-channel concatenation: "desc"),
     CPU tensors, non-contiguous parameters and a homography that is not float32 [B, 3, 3] raise ValueError."""
 
+    _WHO = "KeypointHeadTrainer"
+
     def __init__(self, model, lr=1e-4, train=HEADS, loc_weight=1.0, descriptor_weight=2.0, score_weight=1.0, keypoint_weight=1.0,
                  relax_field=4, betas=(0.9, 0.999), eps=1e-8):
         self.train = _check_model(model, train)
-        if not (lr >= 0 and 0 <= betas[0] < 1 and 0 <= betas[1] < 1 and eps >= 0):
-            raise ValueError(f"KeypointHeadTrainer: lr {lr}, betas {betas}, eps {eps}")
+        self._init_adam(lr, betas, eps)
         self.weights = tuple(float(v) for v in (loc_weight, descriptor_weight, score_weight, keypoint_weight))
         if not all(0 <= v < float("inf") for v in self.weights + (float(relax_field),)):
             raise ValueError(f"KeypointHeadTrainer: the weights {self.weights} and relax_field {relax_field} must be finite and >= 0")
-        self.model, self.lr, self.betas, self.eps, self.relax_field = model, float(lr), tuple(betas), float(eps), relax_field
+        self.model, self.relax_field = model, relax_field
         self.slope = LEAKY_SLOPE if getattr(model, "leaky_relu", True) else 0.0
-        self.steps = 0
         self.parts = self.recall = self.valid = None
-        self._state = {}
 
     @staticmethod
     def _simple(head):
@@ -213,16 +212,9 @@ class KeypointHeadTrainer:
                     d.confAa.conv.weight, d.confAa.bn.weight, d.confAa.bn.bias, d.confBb.weight, d.confBb.bias]
         return out
 
-    def _moments(self, p):
-        st = self._state.get(id(p))
-        if st is None or st[0].device != p.device or st[0].shape != p.shape:
-            st = (torch.zeros_like(p.data), torch.zeros_like(p.data))
-            self._state[id(p)] = st
-        return st
-
     def _check_maps(self, x, skip):
         who = "KeypointHeadTrainer"
-        _st._f32_maps(who, (("x", x), ("skip", skip)))
+        _ops._f32_maps(who, (("x", x), ("skip", skip)))
         c4 = self.model.score_head.convDa.conv.weight.shape[1]
         c_skip = self.model.desc_head.confAa.conv.weight.shape[1] - self.model.desc_head.convB.weight.shape[0] // 4
         N, _, H, W = x.shape
@@ -230,19 +222,15 @@ class KeypointHeadTrainer:
             raise ValueError(f"{who}: needs x [N, {c4}, Hc, Wc] and skip [N, {c_skip}, 2 Hc, 2 Wc] (model.backbone_maps), got "
                              f"{tuple(x.shape)}, {tuple(skip.shape)}")
 
-    def _cbr(self, layer, x):
-        vec = bn_vectors(layer.bn)
-        y, c = cbr_forward(x, layer.conv.weight, vec[0], vec[1], self.slope)
-        return (x, y, c, vec)
-
     def _forward(self, x, skip):
         m = self.model
         x, skip = x.contiguous(), skip.contiguous()
-        a = {"score": self._cbr(m.score_head.convDa, x), "loc": self._cbr(m.loc_head.convDa, x), "descA": self._cbr(m.desc_head.convA, x)}
+        a = {"score": cbr_layer_forward(m.score_head.convDa, x, self.slope), "loc": cbr_layer_forward(m.loc_head.convDa, x, self.slope),
+             "descA": cbr_layer_forward(m.desc_head.convA, x, self.slope)}
         score = torch.sigmoid(conv_bias_forward(a["score"][1], m.score_head.convDb.weight, m.score_head.convDb.bias))
         shift = torch.tanh(conv_bias_forward(a["loc"][1], m.loc_head.convDb.weight, m.loc_head.convDb.bias))
         up = conv_bias_forward(a["descA"][1], m.desc_head.convB.weight, m.desc_head.convB.bias)
-        a["descAa"] = self._cbr(m.desc_head.confAa, shuffle_cat_forward(up, skip))
+        a["descAa"] = cbr_layer_forward(m.desc_head.confAa, shuffle_cat_forward(up, skip), self.slope)
         feat = conv_bias_forward(a["descAa"][1], m.desc_head.confBb.weight, m.desc_head.confBb.bias)
         return {"score": score, "coord": shift, "feat": feat}, a
 
@@ -251,10 +239,6 @@ class KeypointHeadTrainer:
         sigmoid, the shift after the tanh, the raw descriptor map."""
         self._check_maps(x, skip)
         return self._forward(x, skip)[0]
-
-    def _back_cbr(self, layer, saved, dy, need_dx):
-        lx, ly, lc, (scale, _, mean, invstd) = saved
-        return cbr_backward(lx, layer.conv.weight, scale, mean, invstd, ly, lc, dy, self.slope, need_dx=need_dx)
 
     def gradients(self, maps, maps_aug, homography, size):
         """One forward, loss and backward without an update -> (loss, outs of the 2 B frames (target view first), the gradients
@@ -269,8 +253,7 @@ class KeypointHeadTrainer:
             raise ValueError(f"{who}: both views must have one size and one device, got {tuple(maps[0].shape)}, {tuple(maps_aug[0].shape)}")
         B = maps[0].shape[0]
         _check_homography(who, homography, B, maps[0].device)
-        if not all(p.is_contiguous() for p in self.parameters()):
-            raise ValueError(f"{who}: the heads' parameters must be contiguous")
+        self._check_contiguous(self.parameters(), "the heads'")
         m = self.model
         outs, a = self._forward(torch.cat([maps[0], maps_aug[0]]), torch.cat([maps[1], maps_aug[1]]))
         loss, g, stats = keypoint_loss({k: v[:B] for k, v in outs.items()}, {k: v[B:] for k, v in outs.items()}, homography, size, m.cell,
@@ -280,7 +263,7 @@ class KeypointHeadTrainer:
 
         def simple(head, saved, dz):
             dw, db, dy = conv_bias_backward(saved[1], head.convDb.weight, dz)
-            return list(self._back_cbr(head.convDa, saved, dy, False)[:3]) + [dw, db]
+            return list(cbr_layer_backward(head.convDa, saved, dy, self.slope, need_dx=False)[:3]) + [dw, db]
 
         if "score" in self.train:       # the sigmoid's and the tanh's derivative: torch element-wise operations
             dz = torch.cat([g["out"]["score"], g["out_aug"]["score"]]) * outs["score"] * (1.0 - outs["score"])
@@ -291,29 +274,24 @@ class KeypointHeadTrainer:
         if "desc" in self.train:
             d = m.desc_head
             dw2, db2, dy = conv_bias_backward(a["descAa"][1], d.confBb.weight, torch.cat([g["out"]["feat"], g["out_aug"]["feat"]]))
-            ga = self._back_cbr(d.confAa, a["descAa"], dy, True)
+            ga = cbr_layer_backward(d.confAa, a["descAa"], dy, self.slope)
             dup = shuffle_cat_backward(ga[3], d.convB.weight.shape[0] // 4)
             dw1, db1, dy = conv_bias_backward(a["descA"][1], d.convB.weight, dup)
-            grads += list(self._back_cbr(d.convA, a["descA"], dy, False)[:3]) + [dw1, db1] + list(ga[:3]) + [dw2, db2]
+            grads += list(cbr_layer_backward(d.convA, a["descA"], dy, self.slope, need_dx=False)[:3]) + [dw1, db1] + list(ga[:3]) + [dw2, db2]
         return loss, outs, grads
 
     def step_features(self, maps, maps_aug, homography, size):
         """``model.backbone_maps`` of the target frames and of the source frames, the homography and the frames' (H, W) -> the
         loss before the update, a device scalar."""
         loss, _, grads = self.gradients(maps, maps_aug, homography, size)
-        self.steps += 1
-        for p, g in zip(self.parameters(), grads):
-            mom, var = self._moments(p)
-            adam_step(p.data, g.view(p.shape), mom, var, self.steps, self.lr, self.betas, self.eps)
-            with torch.no_grad():     # ``p.data`` counts versions on its own: bump the parameter's, which the engine watches
-                torch.autograd.graph.increment_version(p)
+        self._apply(self.parameters(), grads)
         return loss
 
     def step(self, frames, frames_aug, homography):
         """Target frames and source frames [B, 3, H, W] and the homography -> the loss before the update.  Runs the frozen
         backbone through ``model.backbone_maps`` for each view."""
         for name, t in (("frames", frames), ("frames_aug", frames_aug)):
-            if not isinstance(t, torch.Tensor) or not _st._is_device(t):
+            if not isinstance(t, torch.Tensor) or not _ops._is_device(t):
                 raise ValueError(f"KeypointHeadTrainer.step: {name} must be a device tensor (there is no CPU path)")
         if tuple(frames.shape) != tuple(frames_aug.shape):
             raise ValueError(f"KeypointHeadTrainer.step: both views must have one size, got {tuple(frames.shape)}, {tuple(frames_aug.shape)}")

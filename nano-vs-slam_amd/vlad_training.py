@@ -2,7 +2,8 @@
 (train_visloc.py:249-282) on the HIP kernels of csrc/vlad_train.hip (kp2d_vlad_forward_train, kp2d_triplet_loss,
 kp2d_vlad_backward, kp2d_adam_step; include/kp2d.h).
 
-* ``netvlad_forward`` / ``triplet_margin_loss`` / ``netvlad_backward`` / ``adam_step`` — the four calls on device tensors.
+* ``netvlad_forward`` / ``triplet_margin_loss`` / ``netvlad_backward`` / ``adam_step`` — the four calls on device tensors;
+  ``adam_step`` and the trainers' Adam core (``AdamTrainer``) live in ``train_ops`` and are imported here.
 * ``NetVLADTrainer`` — forward, loss, backward and Adam for ``vlad_head.netvlad.conv.weight`` and
   ``vlad_head.netvlad.centroids`` of a KP2DTiny model; the step's own calls make no host synchronisation.
 
@@ -20,6 +21,7 @@ import torch
 
 from . import _dev, _lib
 from ._dev import ptr as _ptr, stream as _stream
+from .train_ops import AdamTrainer, adam_step  # noqa: F401  (adam_step: this module's fourth call, as it always was)
 
 MAX_KC = 8192
 
@@ -137,28 +139,7 @@ def netvlad_backward(enc, weight, centroids, saved, dvlad, scratch=None):
     return dW, dcent
 
 
-def adam_step(param, grad, exp_avg, exp_avg_sq, step, lr=1e-4, betas=(0.9, 0.999), eps=1e-8):
-    """torch.optim.Adam's update (no weight decay, no amsgrad) of ``param`` and its two moment buffers in place;
-    ``step`` counts from 1.  The kernel writes through raw pointers, so afterwards the tensors' version counters are bumped:
-    whatever caches by version (the engine's packed weights) sees the change."""
-    tensors = (("param", param), ("grad", grad), ("exp_avg", exp_avg), ("exp_avg_sq", exp_avg_sq))
-    for name, t in tensors:
-        _dev.require_device(f"adam_step: {name}", t)
-    for name, t in tensors:
-        if t.dtype != torch.float32 or t.numel() != param.numel() or t.device != param.device or not t.is_contiguous():
-            raise ValueError(f"adam_step: {name} must be a contiguous float32 tensor of {param.numel()} elements on {param.device}")
-    if int(step) < 1:
-        raise ValueError("adam_step: steps count from 1")
-    lib = _lib.load()
-    _lib.check(lib.kp2d_adam_step(_ptr(param), _ptr(grad), _ptr(exp_avg), _ptr(exp_avg_sq), param.numel(), int(step), float(lr),
-                                  float(betas[0]), float(betas[1]), float(eps), _stream(param.device)))
-    with torch.no_grad():
-        for t in (param, exp_avg, exp_avg_sq):
-            torch.autograd.graph.increment_version(t)
-    return param
-
-
-class NetVLADTrainer:
+class NetVLADTrainer(AdamTrainer):
     """Adam on the NetVLAD layer of ``model`` under the reference's triplet loss.
 
         trainer = NetVLADTrainer(model, lr=1e-4, margin=0.1)
@@ -172,28 +153,20 @@ class NetVLADTrainer:
     being frozen, a loop over ``step_encoded`` on encoder maps computed once does not.
     GeM / ConvAP poolers and ``remove_netvlad`` models raise ValueError."""
 
+    _WHO = "NetVLADTrainer"
+
     def __init__(self, model, lr=1e-4, margin=0.1, betas=(0.9, 0.999), eps=1e-8):
         if getattr(model, "global_descriptor_method", None) != "netvlad":
             raise ValueError(f"NetVLADTrainer needs a NetVLAD pooler, the model has {getattr(model, 'global_descriptor_method', None)!r}")
         if getattr(model, "remove_netvlad", False) or not hasattr(model.vlad_head, "netvlad"):
             raise ValueError("NetVLADTrainer: the model was built with remove_netvlad")
-        if not (lr >= 0 and margin >= 0 and 0 <= betas[0] < 1 and 0 <= betas[1] < 1 and eps >= 0):
-            raise ValueError(f"NetVLADTrainer: lr {lr}, margin {margin}, betas {betas}, eps {eps}")
-        self.model, self.lr, self.margin, self.betas, self.eps = model, float(lr), float(margin), tuple(betas), float(eps)
-        self.steps = 0
+        self._init_adam(lr, betas, eps, margin)
+        self.model = model
         self.n_active = None          # device int32 scalar of the last step
-        self._state = {}
 
     @property
     def layer(self):
         return self.model.vlad_head.netvlad
-
-    def _moments(self, p):
-        st = self._state.get(id(p))
-        if st is None or st[0].device != p.device or st[0].shape != p.shape:
-            st = (torch.zeros_like(p.data), torch.zeros_like(p.data))
-            self._state[id(p)] = st
-        return st
 
     def step(self, query, positives, negatives, neg_counts):
         """Frames [B, 3, H, W], [B, 3, H, W], [n_neg, 3, H, W] and the negatives per query -> the loss before the update."""
@@ -209,17 +182,11 @@ class NetVLADTrainer:
         """``enc`` = ``model.only_encoder`` of (queries, positives, negatives) -> the loss before the update."""
         weight, cent = self.layer.conv.weight, self.layer.centroids
         x, w, N, S, C, K = _check_layer(enc, weight, cent)
-        if not (weight.is_contiguous() and cent.is_contiguous()):
-            raise ValueError("NetVLADTrainer: the layer's parameters must be contiguous")
+        self._check_contiguous((weight, cent), "the layer's")
         lib = _lib.load()
         scratch = _scratch(lib, N, S, C, K, x.device)
         vlad, saved = netvlad_forward(x, w, cent, scratch)
         loss, dvlad, self.n_active = triplet_margin_loss(vlad, B, neg_counts, self.margin, scratch)
         dW, dcent = netvlad_backward(x, w, cent, saved, dvlad, scratch)
-        self.steps += 1
-        for p, g in ((weight, dW), (cent, dcent)):
-            m, v = self._moments(p)
-            adam_step(p.data, g, m, v, self.steps, self.lr, self.betas, self.eps)
-            with torch.no_grad():     # ``p.data`` counts versions on its own: bump the parameter's, which the engine watches
-                torch.autograd.graph.increment_version(p)       # (_weights_signature: it re-packs its weights)
+        self._apply((weight, cent), (dW, dcent))
         return loss

@@ -5,6 +5,8 @@ kp2d_vlad_backward_input and the four calls of ``vlad_training``; include/kp2d.h
 * ``cbr_forward`` / ``cbr_backward`` / ``netvlad_backward_input`` — the three layer calls on device tensors.
 * ``cbr_forward_batch`` / ``cbr_backward_batch`` / ``dropout2d_scale`` — the layer on the batch's own statistics, and the
   Dropout2d factors (kp2d_cbr_forward_batchnorm, kp2d_cbr_backward_batchnorm, kp2d_dropout2d_mask).
+  The cbr calls, ``dropout2d_scale``, ``bn_vectors`` and ``adam_step`` live in ``train_ops`` and are imported here;
+  ``netvlad_backward_input`` is this module's own.
 * ``VPRHeadTrainer`` — forward, loss, backward and Adam for ``vlad_head.convlad{1,2,3}.conv.weight``, ``.bn.weight``,
   ``.bn.bias``, ``vlad_head.netvlad.conv.weight`` and ``vlad_head.netvlad.centroids`` of a KP2DTiny model; the step's own
   calls make no host synchronisation.
@@ -28,186 +30,9 @@ import torch
 
 from . import _dev, _lib
 from ._dev import ptr as _ptr, stream as _stream
-from .vlad_training import (_check_layer, _scratch as _vlad_scratch, adam_step, netvlad_backward, netvlad_forward,
-                            triplet_margin_loss)
-
-MIN_CH, MAX_CH = 16, 128
-LEAKY_SLOPE = 0.01          # nn.LeakyReLU's default, the reference's (modules/base.py:33)
-
-
-def _check_cbr(x, weight, vectors, maps=()):
-    """-> (N, H, W, Cin, Cout); placement first, then shapes: all before any library call.  ``vectors``: (name, tensor)
-    per-channel [Cout]; ``maps``: (name, tensor) of the output's shape [N, Cout, H, W]."""
-    named = (("x", x), ("weight", weight)) + tuple(vectors) + tuple(maps)
-    for name, t in named:
-        _dev.require_device(f"vpr_head_training: {name}", t)
-    if x.dim() != 4 or x.dtype != torch.float32:
-        raise ValueError(f"x must be float32 [N, Cin, H, W], got {x.dtype} {tuple(x.shape)}")
-    N, Cin, H, W = x.shape
-    if weight.dim() != 4 or weight.dtype != torch.float32 or weight.shape[1:] != (Cin, 3, 3):
-        raise ValueError(f"weight must be float32 [Cout, {Cin}, 3, 3], got {weight.dtype} {tuple(weight.shape)}")
-    Cout = weight.shape[0]
-    if N < 1 or N > 65535 or H < 1 or W < 1:
-        raise ValueError(f"x must be [1 <= N <= 65535, Cin, H >= 1, W >= 1], got {tuple(x.shape)}")
-    if Cin % 16 or Cout % 16 or not (MIN_CH <= Cin <= MAX_CH and MIN_CH <= Cout <= MAX_CH):
-        raise ValueError(f"head training needs Cin % 16 == 0, Cout % 16 == 0 and {MIN_CH} <= Cin, Cout <= {MAX_CH} "
-                         f"(got Cin {Cin}, Cout {Cout})")
-    for name, t in vectors:
-        if tuple(t.shape) != (Cout,) or t.dtype != torch.float32:
-            raise ValueError(f"{name} must be float32 [{Cout}], got {t.dtype} {tuple(t.shape)}")
-    for name, t in maps:
-        if tuple(t.shape) != (N, Cout, H, W) or t.dtype != torch.float32:
-            raise ValueError(f"{name} must be float32 {(N, Cout, H, W)}, got {t.dtype} {tuple(t.shape)}")
-    if any(t.device != x.device for _, t in named):
-        raise ValueError("every tensor of a layer call must live on one device")
-    return N, H, W, Cin, Cout
-
-
-def _check_slope(slope):
-    slope = float(slope)
-    if not 0.0 <= slope < 1.0:
-        raise ValueError(f"slope must be in [0, 1), got {slope}")
-    return slope
-
-
-def _scratch(lib, N, H, W, Cin, Cout, dev):
-    nbytes = int(lib.kp2d_cbr_train_scratch_bytes(N, H, W, Cin, Cout))
-    if nbytes == 0:
-        raise ValueError(f"head training does not support N {N}, H {H}, W {W}, Cin {Cin}, Cout {Cout}")
-    return _dev.scratch(nbytes, dev)
-
-
-def bn_vectors(bn):
-    """A BatchNorm2d on its running statistics as the four per-channel vectors the layer calls take ->
-    (scale = gamma / sqrt(var + eps), shift = beta - mean scale, mean, invstd = 1 / sqrt(var + eps)).  Formed with torch on
-    the parameters' device."""
-    with torch.no_grad():
-        invstd = 1.0 / torch.sqrt(bn.running_var.float() + bn.eps)
-        scale = bn.weight.detach().float() * invstd
-        mean = bn.running_mean.float().contiguous()
-        shift = bn.bias.detach().float() - mean * scale
-    return scale.contiguous(), shift.contiguous(), mean, invstd.contiguous()
-
-
-def cbr_forward(x, weight, scale, shift, slope=LEAKY_SLOPE, scratch=None):
-    """x [N, Cin, H, W], weight [Cout, Cin, 3, 3], scale and shift [Cout] -> (y, c), both [N, Cout, H, W]:
-    c = conv3x3(x, weight) (stride 1, padding 1, no bias) and y = act(scale c + shift), act(v) = v if v > 0 else slope v
-    (slope 0.01: LeakyReLU, 0: ReLU).  ``c`` is what ``cbr_backward`` reads."""
-    N, H, W, Cin, Cout = _check_cbr(x, weight, (("scale", scale), ("shift", shift)))
-    slope = _check_slope(slope)
-    x, w = x.contiguous(), weight.detach().contiguous()
-    lib = _lib.load()
-    scratch = _scratch(lib, N, H, W, Cin, Cout, x.device) if scratch is None else scratch
-    y = torch.empty(N, Cout, H, W, dtype=torch.float32, device=x.device)
-    c = torch.empty_like(y)
-    _lib.check(lib.kp2d_cbr_forward_train(_ptr(x), _ptr(w), _ptr(scale.contiguous()), _ptr(shift.contiguous()), slope, N, H, W,
-                                          Cin, Cout, _ptr(y), _ptr(c), _ptr(scratch), scratch.numel(), _stream(x.device)))
-    return y, c
-
-
-def cbr_backward(x, weight, scale, mean, invstd, y, c, dy, slope=LEAKY_SLOPE, need_dx=True, scratch=None):
-    """The gradients of a scalar given its gradient ``dy`` with respect to ``cbr_forward``'s ``y`` ->
-    (dweight [Cout, Cin, 3, 3], dgamma [Cout], dbeta [Cout], dx [N, Cin, H, W] or None when ``need_dx`` is false).
-    dgamma is formed from ``c`` itself, so it is right for a channel whose gamma is 0.  Bit-reproducible, and dweight, dgamma
-    and dbeta have the same bits with and without dx."""
-    N, H, W, Cin, Cout = _check_cbr(x, weight, (("scale", scale), ("mean", mean), ("invstd", invstd)),
-                                    (("y", y), ("c", c), ("dy", dy)))
-    slope = _check_slope(slope)
-    x, w = x.contiguous(), weight.detach().contiguous()
-    lib = _lib.load()
-    scratch = _scratch(lib, N, H, W, Cin, Cout, x.device) if scratch is None else scratch
-    dw = torch.empty(Cout, Cin, 3, 3, dtype=torch.float32, device=x.device)
-    dgamma = torch.empty(Cout, dtype=torch.float32, device=x.device)
-    dbeta = torch.empty_like(dgamma)
-    dx = torch.empty_like(x) if need_dx else None
-    _lib.check(lib.kp2d_cbr_backward(_ptr(x), _ptr(w), _ptr(scale.contiguous()), _ptr(mean.contiguous()), _ptr(invstd.contiguous()),
-                                     slope, _ptr(y.contiguous()), _ptr(c.contiguous()), _ptr(dy.contiguous()), N, H, W, Cin, Cout,
-                                     _ptr(dw), _ptr(dgamma), _ptr(dbeta), _ptr(dx), _ptr(scratch), scratch.numel(),
-                                     _stream(x.device)))
-    return dw, dgamma, dbeta, dx
-
-
-def _check_drop(drop, N, Cout, x):
-    if drop is None:
-        return None
-    _dev.require_device("vpr_head_training: drop", drop)
-    if tuple(drop.shape) != (N, Cout) or drop.dtype != torch.float32 or drop.device != x.device:
-        raise ValueError(f"drop must be float32 {(N, Cout)} on {x.device}, got {drop.dtype} {tuple(drop.shape)} on {drop.device}")
-    return drop.contiguous()
-
-
-def cbr_forward_batch(x, weight, gamma, beta, eps=1e-5, slope=LEAKY_SLOPE, drop=None, running=None, momentum=0.1, scratch=None):
-    """``cbr_forward`` with BatchNorm on the batch's own statistics -> (y, c, mean, invstd): over the M = N H W values of a
-    channel, mean = sum c / M, var = sum (c - mean)^2 / M (biased), invstd = 1 / sqrt(var + eps),
-    y = act(gamma invstd (c - mean) + beta) drop[n, co].  ``drop``: [N, Cout] of 0 or 1 / (1 - p) (``dropout2d_scale``), None:
-    no dropout.  ``running`` = (running_mean, running_var), float32 [Cout] contiguous, updated in place on the device:
-    (1 - momentum) running + momentum (mean, var M / (M - 1)).  M < 2 raises, as torch does."""
-    vectors = (("gamma", gamma), ("beta", beta)) + ((("running_mean", running[0]), ("running_var", running[1])) if running is not None else ())
-    N, H, W, Cin, Cout = _check_cbr(x, weight, vectors)
-    slope = _check_slope(slope)
-    eps, momentum = float(eps), float(momentum)
-    if not (0.0 <= eps < float("inf") and 0.0 <= momentum <= 1.0):
-        raise ValueError(f"eps must be finite and >= 0 and momentum in [0, 1], got {eps}, {momentum}")
-    if N * H * W < 2:
-        raise ValueError(f"batch statistics need more than 1 value per channel, got x {tuple(x.shape)}")
-    if running is not None and not all(t.is_contiguous() for t in running):
-        raise ValueError("running_mean and running_var must be contiguous: they are updated in place")
-    drop = _check_drop(drop, N, Cout, x)
-    x, w = x.contiguous(), weight.detach().contiguous()
-    lib = _lib.load()
-    scratch = _scratch(lib, N, H, W, Cin, Cout, x.device) if scratch is None else scratch
-    y = torch.empty(N, Cout, H, W, dtype=torch.float32, device=x.device)
-    c = torch.empty_like(y)
-    mean = torch.empty(Cout, dtype=torch.float32, device=x.device)
-    invstd = torch.empty_like(mean)
-    rm, rv = (running[0].detach(), running[1].detach()) if running is not None else (None, None)
-    _lib.check(lib.kp2d_cbr_forward_batchnorm(_ptr(x), _ptr(w), _ptr(gamma.detach().contiguous()), _ptr(beta.detach().contiguous()), eps,
-                                              slope, _ptr(drop), momentum, _ptr(rm), _ptr(rv), N, H, W, Cin, Cout, _ptr(y), _ptr(c),
-                                              _ptr(mean), _ptr(invstd), _ptr(scratch), scratch.numel(), _stream(x.device)))
-    return y, c, mean, invstd
-
-
-def cbr_backward_batch(x, weight, gamma, mean, invstd, y, c, dy, slope=LEAKY_SLOPE, drop=None, need_dx=True, scratch=None):
-    """``cbr_backward`` for ``cbr_forward_batch`` (its mean, invstd, y, c and the same ``drop``) -> (dweight, dgamma, dbeta, dx
-    or None): g = dy drop (y > 0 ? 1 : slope), dbeta = sum g, dgamma = sum g xhat, dc = gamma invstd (g - dbeta / M -
-    xhat dgamma / M) with xhat = (c - mean) invstd: the two terms through the batch mean and variance included.
-    Bit-reproducible, and dweight, dgamma and dbeta have the same bits with and without dx."""
-    N, H, W, Cin, Cout = _check_cbr(x, weight, (("gamma", gamma), ("mean", mean), ("invstd", invstd)), (("y", y), ("c", c), ("dy", dy)))
-    slope = _check_slope(slope)
-    if N * H * W < 2:
-        raise ValueError(f"batch statistics need more than 1 value per channel, got x {tuple(x.shape)}")
-    drop = _check_drop(drop, N, Cout, x)
-    x, w = x.contiguous(), weight.detach().contiguous()
-    lib = _lib.load()
-    scratch = _scratch(lib, N, H, W, Cin, Cout, x.device) if scratch is None else scratch
-    dw = torch.empty(Cout, Cin, 3, 3, dtype=torch.float32, device=x.device)
-    dgamma = torch.empty(Cout, dtype=torch.float32, device=x.device)
-    dbeta = torch.empty_like(dgamma)
-    dx = torch.empty_like(x) if need_dx else None
-    _lib.check(lib.kp2d_cbr_backward_batchnorm(_ptr(x), _ptr(w), _ptr(gamma.detach().contiguous()), _ptr(mean.contiguous()),
-                                               _ptr(invstd.contiguous()), slope, _ptr(drop), _ptr(y.contiguous()), _ptr(c.contiguous()),
-                                               _ptr(dy.contiguous()), N, H, W, Cin, Cout, _ptr(dw), _ptr(dgamma), _ptr(dbeta), _ptr(dx),
-                                               _ptr(scratch), scratch.numel(), _stream(x.device)))
-    return dw, dgamma, dbeta, dx
-
-
-def dropout2d_scale(N, C, p, seed, step, layer, device):
-    """The Dropout2d factors of one step -> float32 [N, C] on ``device``: 0 for a dropped (frame, channel) plane, 1 / (1 - p)
-    for a kept one.  A counter-based draw of (seed, step, layer, n, c) (include/kp2d.h states the layout), not torch's
-    random stream: the same arguments give the same mask anywhere."""
-    N, C, p, seed, step, layer = int(N), int(C), float(p), int(seed), int(step), int(layer)
-    if N < 1 or C < 1 or N * C >= 2 ** 31:
-        raise ValueError(f"dropout2d_scale needs N, C >= 1 and N * C < 2^31, got {N}, {C}")
-    if not 0.0 <= p < 1.0:
-        raise ValueError(f"dropout2d_scale: p must be in [0, 1), got {p}")
-    if not (0 <= seed < 2 ** 64 and 0 <= step < 2 ** 32 and 0 <= layer < 2 ** 31):
-        raise ValueError(f"dropout2d_scale: seed {seed} outside [0, 2^64), step {step} outside [0, 2^32) or layer {layer} outside [0, 2^31)")
-    device = torch.device(device)
-    if device.type != "cuda":
-        raise RuntimeError(f"dropout2d_scale: there is no CPU path, got device {device}")
-    drop = torch.empty(N, C, dtype=torch.float32, device=device)
-    _lib.check(_lib.load().kp2d_dropout2d_mask(_ptr(drop), N, C, p, seed, step, layer, _stream(drop.device)))
-    return drop
+from .train_ops import (LEAKY_SLOPE, MAX_CH, MIN_CH, AdamTrainer, _cbr_scratch, adam_step, bn_vectors, cbr_backward,  # noqa: F401
+                        cbr_backward_batch, cbr_forward, cbr_forward_batch, cbr_layer_backward, cbr_layer_forward, dropout2d_scale)
+from .vlad_training import _check_layer, _scratch as _vlad_scratch, netvlad_backward, netvlad_forward, triplet_margin_loss
 
 
 def netvlad_backward_input(enc, weight, centroids, saved, dvlad, scratch=None):
@@ -229,7 +54,7 @@ def netvlad_backward_input(enc, weight, centroids, saved, dvlad, scratch=None):
     return dx.view(enc.shape)
 
 
-class VPRHeadTrainer:
+class VPRHeadTrainer(AdamTrainer):
     """Adam on the whole ``vlad_head`` of ``model`` under the reference's triplet loss.
 
         trainer = VPRHeadTrainer(model, lr=1e-4, margin=0.1)
@@ -252,14 +77,15 @@ class VPRHeadTrainer:
     ``backbone_features`` is such a call, so a loop over ``step`` pays that upload once per step and a loop over
     ``step_features`` does not.  GeM / ConvAP poolers and ``remove_netvlad`` models raise ValueError."""
 
+    _WHO = "VPRHeadTrainer"
+
     def __init__(self, model, lr=1e-4, margin=0.1, betas=(0.9, 0.999), eps=1e-8, bn="running", dropout=0.0, seed=0):
         if getattr(model, "global_descriptor_method", None) != "netvlad":
             raise ValueError(f"VPRHeadTrainer needs a NetVLAD pooler, the model has {getattr(model, 'global_descriptor_method', None)!r}")
         if getattr(model, "remove_netvlad", False) or not hasattr(model.vlad_head, "netvlad"):
             raise ValueError("VPRHeadTrainer: the model was built with remove_netvlad")
-        if not (lr >= 0 and margin >= 0 and 0 <= betas[0] < 1 and 0 <= betas[1] < 1 and eps >= 0):
-            raise ValueError(f"VPRHeadTrainer: lr {lr}, margin {margin}, betas {betas}, eps {eps}")
-        self.model, self.lr, self.margin, self.betas, self.eps = model, float(lr), float(margin), tuple(betas), float(eps)
+        self._init_adam(lr, betas, eps, margin)
+        self.model = model
         self.slope = LEAKY_SLOPE if getattr(model, "leaky_relu", True) else 0.0
         if bn not in ("running", "batch"):
             raise ValueError(f"VPRHeadTrainer: bn must be 'running' or 'batch', got {bn!r}")
@@ -270,9 +96,7 @@ class VPRHeadTrainer:
         if bn == "batch" and any(layer.bn.momentum is None for layer in self.layers):
             raise ValueError("VPRHeadTrainer: bn='batch' needs a numeric bn.momentum (None, the cumulative average, is not built)")
         self.bn, self.dropout, self.seed = bn, float(dropout), int(seed)
-        self.steps = 0
         self.n_active = None          # device int32 scalar of the last step
-        self._state = {}
 
     @property
     def layers(self):
@@ -286,13 +110,6 @@ class VPRHeadTrainer:
             out += [layer.conv.weight, layer.bn.weight, layer.bn.bias]
         netvlad = self.model.vlad_head.netvlad
         return out + [netvlad.conv.weight, netvlad.centroids]
-
-    def _moments(self, p):
-        st = self._state.get(id(p))
-        if st is None or st[0].device != p.device or st[0].shape != p.shape:
-            st = (torch.zeros_like(p.data), torch.zeros_like(p.data))
-            self._state[id(p)] = st
-        return st
 
     def step(self, query, positives, negatives, neg_counts):
         """Frames [B, 3, H, W], [B, 3, H, W], [n_neg, 3, H, W] and the negatives per query -> the loss before the update."""
@@ -311,10 +128,8 @@ class VPRHeadTrainer:
         ``drop``: the [N, C] factors behind ``convlad1``, None: no dropout."""
         acts, x = [], feat
         for i, layer in enumerate(self.layers):
-            vec = bn_vectors(layer.bn)
-            y, c = cbr_forward(x, layer.conv.weight, vec[0], vec[1], self.slope, scratch)
-            acts.append((x, y, c, vec))
-            x = y if i > 0 or drop is None else y * drop[:, :, None, None]
+            acts.append(cbr_layer_forward(layer, x, self.slope, scratch))
+            x = acts[-1][1] if i > 0 or drop is None else acts[-1][1] * drop[:, :, None, None]
         return acts
 
     def _forward_batch(self, feat, scratch, drop):
@@ -336,8 +151,7 @@ class VPRHeadTrainer:
         _dev.require_device("VPRHeadTrainer.step_features: feat", feat)
         if feat.dim() != 4 or feat.dtype != torch.float32 or feat.shape[1] != self.layers[0].conv.weight.shape[1]:
             raise ValueError(f"feat must be float32 [N, {self.layers[0].conv.weight.shape[1]}, Hc, Wc], got {feat.dtype} {tuple(feat.shape)}")
-        if not all(p.is_contiguous() for p in params):
-            raise ValueError("VPRHeadTrainer: the head's parameters must be contiguous")
+        self._check_contiguous(params, "the head's")
         netvlad = self.model.vlad_head.netvlad
         weight, cent = netvlad.conv.weight, netvlad.centroids
         lib = _lib.load()
@@ -346,7 +160,7 @@ class VPRHeadTrainer:
         if batch and N * H * W < 2:
             raise ValueError(f"bn='batch' needs more than 1 value per channel, got feat {tuple(feat.shape)}")
         cmax = max(max(l.conv.weight.shape[:2]) for l in self.layers)
-        scratch = _scratch(lib, N, H, W, cmax, cmax, feat.device)        # the largest layer's: every layer call fits
+        scratch = _cbr_scratch(lib, N, H, W, cmax, cmax, feat.device)        # the largest layer's: every layer call fits
         if drop is None and self.dropout > 0:
             drop = dropout2d_scale(N, self.layers[0].conv.weight.shape[0], self.dropout, self.seed, self.steps + 1, 1, feat.device)
         if batch:
@@ -368,18 +182,12 @@ class VPRHeadTrainer:
                 dw, dgamma, dbeta, dy = cbr_backward_batch(lx, layer.conv.weight, layer.bn.weight, mean, invstd, ly, lc, dy, self.slope,
                                                            drop if i == 0 else None, need_dx=i > 0, scratch=scratch)
             else:
-                lx, ly, lc, (scale, _, mean, invstd) = acts[i]
                 if i == 0 and drop is not None:
                     dy = dy * drop[:, :, None, None]
-                dw, dgamma, dbeta, dy = cbr_backward(lx, layer.conv.weight, scale, mean, invstd, ly, lc, dy, self.slope,
-                                                     need_dx=i > 0, scratch=scratch)      # (the backbone is frozen: no dx of layer 1)
+                dw, dgamma, dbeta, dy = cbr_layer_backward(layer, acts[i], dy, self.slope, need_dx=i > 0,
+                                                           scratch=scratch)               # (the backbone is frozen: no dx of layer 1)
             grads[3 * i:3 * i + 3] = [dw, dgamma, dbeta]
-        self.steps += 1
-        for p, g in zip(params, grads):
-            m, v = self._moments(p)
-            adam_step(p.data, g.view(p.shape), m, v, self.steps, self.lr, self.betas, self.eps)
-            with torch.no_grad():     # ``p.data`` counts versions on its own: bump the parameter's, which the engine watches
-                torch.autograd.graph.increment_version(p)
+        self._apply(params, grads)
         if batch:
             with torch.no_grad():     # the kernel wrote the running statistics through their addresses: bump those too
                 for layer in self.layers:

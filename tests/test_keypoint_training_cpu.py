@@ -163,7 +163,7 @@ def no_library(monkeypatch):
 
 @pytest.fixture
 def shapes_only(no_library, monkeypatch):
-    monkeypatch.setattr(st, "_is_device", lambda t: True)       # shapes, on a box without a device
+    monkeypatch.setattr("nano_vs_slam_amd.train_ops._is_device", lambda t: True)     # shapes, on a box without a device
 
 
 def _model(config="S", **kw):
