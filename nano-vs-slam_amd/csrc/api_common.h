@@ -1,5 +1,5 @@
 // What every host file behind the C ABI shares: the thread-local error message, HIP_TRY and the workspace alignment.
-// No HIP header here (model_desc.cpp compiles without one); HIP_TRY expands where <hip/hip_runtime.h> is included.
+// No HIP header here (model_desc.cpp and lightglue_desc.cpp compile without one); HIP_TRY expands where <hip/hip_runtime.h> is included.
 #pragma once
 #include <cstdarg>
 #include <cstddef>

@@ -14,6 +14,7 @@
 #include "device_guard.h"
 #include "kp2d_kernels.h"
 #include "plan.h"
+#include "weight_upload.h"
 
 using namespace kp2d;
 using namespace kp2d::plan;
@@ -78,38 +79,26 @@ int kp2d_num_weights(const kp2d_model* m) { return m ? (int)m->specs.size() : 0;
 
 int kp2d_weight_info(const kp2d_model* m, int index, const char** key, int64_t shape[4], int* ndim) {
   if (!m || index < 0 || index >= (int)m->specs.size()) return fail(KP2D_ERR_ARG, "weight index out of range");
-  const WeightSpec& s = m->specs[index];
-  if (key) *key = s.key.c_str();
-  if (ndim) *ndim = (int)s.shape.size();
-  if (shape) for (size_t i = 0; i < s.shape.size() && i < 4; ++i) shape[i] = s.shape[i];
+  weight_info(m->specs, index, key, shape, ndim, /*pad_shape=*/false);
   return KP2D_OK;
 }
 
 int kp2d_set_weight(kp2d_model* m, const char* key, const float* host, const int64_t* shape, int ndim) {
   if (!m || !key || !host || (!shape && ndim > 0)) return fail(KP2D_ERR_ARG, "null argument");
   std::string k(key);
-  if (k.size() > 20 && k.compare(k.size() - 20, 20, ".num_batches_tracked") == 0) return KP2D_OK;
-  auto it = m->spec_index.find(k);
-  if (it == m->spec_index.end()) return fail(KP2D_ERR_WEIGHT, "unexpected key '%s'", key);
-  const WeightSpec& s = m->specs[it->second];
-  bool same = (int)s.shape.size() == ndim;
-  for (int i = 0; same && i < ndim; ++i) same = s.shape[i] == shape[i];
-  if (!same) return fail(KP2D_ERR_WEIGHT, "shape mismatch for '%s'", key);
-  m->host[k].assign(host, host + s.numel());
-  m->finalized = false;
-  return KP2D_OK;
+  if (k.size() > 20 && k.compare(k.size() - 20, 20, ".num_batches_tracked") == 0) return KP2D_OK;      // BatchNorm's step counter
+  const int rc = set_weight(m->specs, m->spec_index, m->host, key, host, shape, ndim);
+  if (rc == KP2D_OK) m->finalized = false;
+  return rc;
 }
 
 int kp2d_finalize_weights(kp2d_model* m) {
   if (!m) return fail(KP2D_ERR_ARG, "null model");
   std::vector<float> blob;
   int rc = pack(m, blob);
-  if (rc != KP2D_OK) return rc;
-  DeviceGuard guard(m->cfg.device);
-  if (!m->blob) HIP_TRY(hipMalloc((void**)&m->blob, m->blob_floats * sizeof(float)));
-  HIP_TRY(hipMemcpy(m->blob, blob.data(), m->blob_floats * sizeof(float), hipMemcpyHostToDevice));
-  m->finalized = true;
-  return KP2D_OK;
+  if (rc == KP2D_OK) rc = upload_blob(m->cfg.device, &m->blob, blob);
+  if (rc == KP2D_OK) m->finalized = true;
+  return rc;
 }
 
 size_t kp2d_packed_bytes(const kp2d_model* m) { return m ? m->blob_floats * sizeof(float) : 0; }

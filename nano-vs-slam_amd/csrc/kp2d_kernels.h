@@ -1,4 +1,4 @@
-// Internal launch interface between the host code (plan.cpp, kp2d_api.cpp, lightglue_api.cpp) and the HIP kernels: only what
+// Internal launch interface between the host code (plan.cpp, kp2d_api.cpp, lightglue_plan.cpp) and the HIP kernels: only what
 // crosses files (match.hip, keypoint_metrics.hip, dense_metrics.hip keep their argument structs and entry points to themselves).
 // Not part of the public ABI (that is include/kp2d.h).
 #pragma once
@@ -153,7 +153,7 @@ int launch_lg_linear(const LgLinArgs& a, hipStream_t s);
 // fused tail of a Self/CrossBlock for D = 32: x += ffn(cat[x, out_proj(ctx)])  (lightglue.py:260-261 / :322-326)
 struct LgTailArgs {
   float* x; const float* ctx;           // [rows][D] in place / attention context (null: projection only)
-  // split-fp16 matrix-core images of W (lightglue_api.cpp mfma_image()) and fp32 biases
+  // split-fp16 matrix-core images of W (lightglue_desc.cpp mfma_image()) and fp32 biases
   const void* io; const float* bo;       // out_proj / to_out  [D -> D]
   const void* i1; const float* b1;       // ffn.0              [2D -> 2D]
   const float* ln_g; const float* ln_b;  // ffn.1

@@ -1,4 +1,4 @@
-// Host-side choice of the launch forms of one LightGlue forward (lightglue_api.cpp run_forward, lightglue.hip
+// Host-side choice of the launch forms of one LightGlue forward (lightglue_plan.cpp run_forward, lightglue.hip
 // launch_lg_tail): fused block tails or the lg_linear chain, projections inside the tails' launches or on their own, waves
 // per tail workgroup, and the sequences each attention launch walks.  Plain C++: the tuning values (options.h Tuning:
 // lg_fuse, lg_fuse_next, lg_tail_nw) are arguments (tests/test_lightglue_forms.py compiles it with g++).

@@ -9,18 +9,9 @@
 #include <vector>
 
 #include "../../include/kp2d.h"
+#include "weight_table.h"
 
 namespace kp2d {
-
-struct WeightSpec {
-  std::string key;
-  std::vector<int64_t> shape;
-  size_t numel() const {
-    size_t n = 1;
-    for (auto s : shape) n *= (size_t)s;
-    return n;
-  }
-};
 
 // one packed 3x3 convolution
 struct ConvPack {
