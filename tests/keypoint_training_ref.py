@@ -72,11 +72,17 @@ def make_loss_inputs(name, seed=None):
     """-> dict(tgt, src: {score [B,1,Hc,Wc], shift [B,2,Hc,Wc], feat [B,C,Hf,Wf]} float32, hom [B,3,3] float32, H, W, cell,
     weights): uniform scores, shifts in +-0.9, normal descriptors.  The source's descriptor map is the target's plus noise
     in its second half of the channels, so that the triplet hinge has both active and inactive anchors."""
-    B, Hc, Wc, cell, C, Hf, Wf, weights = LOSS_CASES[name]
-    rng = np.random.default_rng(seed_of(name) if seed is None else seed)
+    return draw_loss_inputs(LOSS_CASES[name], seed_of(name) if seed is None else seed, strong=(1,) if name == "C" else ())
+
+
+def draw_loss_inputs(shape, seed, strong=()):
+    """make_loss_inputs' draw for any (B, Hc, Wc, cell, C, Hf, Wf, weights); ``strong``: the pairs under case C's strong
+    homography."""
+    B, Hc, Wc, cell, C, Hf, Wf, weights = shape
+    rng = np.random.default_rng(seed)
     tgt, src = _views(rng, B, Hc, Wc, C, Hf, Wf)
     src["feat"] = (0.6 * tgt["feat"] + 0.8 * src["feat"]).astype(np.float32)
-    hom = _homographies(rng, B, strong=(1,) if name == "C" else ())
+    hom = _homographies(rng, B, strong=strong)
     return {"tgt": tgt, "src": src, "hom": hom, "H": Hc * cell, "W": Wc * cell, "cell": cell, "weights": weights}
 
 
@@ -119,12 +125,17 @@ def sample_backward(g, nx, ny, shape):
     return d
 
 
-def keypoint_loss(tgt, src, hom, H, W, cell, weights=WEIGHTS, relax=RELAX, cross_ratio=CROSS_RATIO, dtype=np.float64, grads=True, grids=None):
+def keypoint_loss(tgt, src, hom, H, W, cell, weights=WEIGHTS, relax=RELAX, cross_ratio=CROSS_RATIO, dtype=np.float64, grads=True, grids=None, blas=True):
     """include/kp2d.h's kp2d_keypoint_loss -> dict(loss, loc, metric, usp, con (unweighted), the six GRADS, M, n, hits, recall,
     usp_abs (the mean of |summand| behind usp), gaps and q (the generator's margins and the quantities they guard)).
     ``dtype=np.float32`` runs the forward quantities in float32 (the generator's estimate of a float32 run's decisions).
     ``grids``: an earlier result's ``["grids"]``, held fixed for the three samplings: the reference detaches them, so a finite
-    difference of the loss agrees with the gradient only when they do not move."""
+    difference of the loss agrees with the gradient only when they do not move.  ``blas=False`` forms the descriptor products
+    elementwise, summed over the channel axis: equal columns then give equal values bit for bit, which a blocked GEMM does not
+    promise.  ``stages`` holds what the device keeps in its scratch: per pair M_b, the matches and the sums fsum[0..4] (sum d,
+    sum S, the consistency sum, sum S (d - mean), the hinge sum; ``usp_abs_b`` the sum of |S (d - mean)|), and per pair of the
+    descriptor term a dict: neg, best, hit, hinge, cn (the negative's coefficient, 0 on an inactive hinge), the normalised
+    rows r and t [n, C], and for the gradient walk the sampled rows, their norms, the points, g_pos and g_neg."""
     f = dtype
     st, ht, ft = (np.asarray(tgt[k], f) for k in ("score", "shift", "feat"))
     ss, hs, fs = (np.asarray(src[k], f) for k in ("score", "shift", "feat"))
@@ -177,7 +188,8 @@ def keypoint_loss(tgt, src, hom, H, W, cell, weights=WEIGHTS, relax=RELAX, cross
     metric, hits = 0.0, 0
     cells = np.flatnonzero(inner)
     dfeat_t, dfeat_s = np.zeros(ft.shape, f), np.zeros(fs.shape, f)
-    neg_gap, hinge_gap, relax_gap = [], [], []
+    neg_gap, hinge_gap, relax_gap, pairs = [], [], [], []
+    hinge_b = np.zeros(B)
     q_dmat, q_harg = [], []
     eps = f(1e-8)
     for b in range(B if do_desc else 0):
@@ -185,10 +197,12 @@ def keypoint_loss(tgt, src, hom, H, W, cell, weights=WEIGHTS, relax=RELAX, cross
         xr, xt = sample(fs[b], *pts[0]), sample(ft[b], *pts[1])
         sr_, st_ = np.sqrt(((xr + eps) ** 2).sum(0)), np.sqrt(((xt + eps) ** 2).sum(0))
         ref, tar = xr / (sr_ + eps), xt / (st_ + eps)
-        dmat = np.sqrt(f(2) - f(2) * np.clip(ref.T @ tar, -1, 1) + eps)
+        dots = ref.T @ tar if blas else (ref.T[:, None, :] * tar.T[None, :, :]).sum(axis=2)
+        dmat = np.sqrt(f(2) - f(2) * np.clip(dots, -1, 1) + eps)
         best = dmat.argmin(axis=1)
         kx, ky = wx[b, cells], wy[b, cells]
-        hits += int(((kx[best] == kx) & (ky[best] == ky)).sum())
+        hit = (kx[best] == kx) & (ky[best] == ky)
+        hits += int(hit.sum())
         ax, ay = np.abs(kx[None, :] - kx[:, None]), np.abs(ky[None, :] - ky[:, None])
         within = (ax <= f(relax)) & (ay <= f(relax))
         masked = np.where(within, np.inf, dmat)
@@ -198,6 +212,9 @@ def keypoint_loss(tgt, src, hom, H, W, cell, weights=WEIGHTS, relax=RELAX, cross
         harg = f(MARGIN) + dp - dn
         hinge = np.maximum(harg, 0)
         metric += float(hinge.astype(np.float64).mean() / B)
+        hinge_b[b] = hinge.astype(np.float64).sum()
+        pairs.append({"neg": neg, "best": best, "hit": hit, "hinge": hinge, "r": ref.T, "t": tar.T, "xr": xr, "xt": xt, "sr": sr_, "st": st_,
+                      "pts": pts, "cn": np.zeros(n, f)})
         part = np.partition(masked, 1, axis=1)[:, :2]
         has_two = np.isfinite(part[:, 1])
         neg_gap.append(np.where(has_two, np.where(has_two, part[:, 1], 0) - np.where(has_two, part[:, 0], 0), np.inf))
@@ -207,16 +224,12 @@ def keypoint_loss(tgt, src, hom, H, W, cell, weights=WEIGHTS, relax=RELAX, cross
         q_dmat.append(dmat)
         q_harg.append(harg)
         if grads:
-            scale = kw * dw * 2.0 / (B * n)
+            scale = f(kw * dw * 2.0 / (B * n))            # (a Python float times the bool ``on`` would be float64 in either mode)
             on = hinge > 0
             g_pos, g_neg = scale * on * ep / np.where(dp > 0, dp, 1), scale * on * en / np.where(dn > 0, dn, 1)
             g_ref, g_tar = g_pos - g_neg, -g_pos
             np.add.at(g_tar.T, neg, g_neg.T)
-
-            def norm_back(g, x, s):
-                D = s + eps
-                return g / D - (g * x).sum(0) / (D * D * s) * (x + eps)
-
+            pairs[-1].update(g_pos=g_pos, g_neg=g_neg, cn=(scale * on / np.where(dn > 0, dn, 1) * (dn > 0)).astype(f))
             dfeat_s[b] = sample_backward(norm_back(g_ref, xr, sr_), *pts[0], fs[b].shape)
             dfeat_t[b] = sample_backward(norm_back(g_tar, xt, st_), *pts[1], ft[b].shape)
 
@@ -224,6 +237,10 @@ def keypoint_loss(tgt, src, hom, H, W, cell, weights=WEIGHTS, relax=RELAX, cross
     out = {"loss": float(loss), "loc": loc, "metric": metric, "usp": usp, "con": con, "usp_abs": usp_abs, "M": M,
            "n": n if do_desc else 0, "hits": hits, "recall": hits / (B * n) if do_desc else 0.0, "a": a, "d": d, "valid": valid,
            "grids": (gnx, gny, gwx_, gwy_)}
+    s64, d64 = S.astype(np.float64) * valid, (d.astype(np.float64) - loc) * valid
+    out["stages"] = {"M_b": valid.sum(axis=1), "fsum": np.stack([(d.astype(np.float64) * valid).sum(axis=1), s64.sum(axis=1),
+                                                                  (diff.astype(np.float64) ** 2).sum(axis=1), (s64 * d64).sum(axis=1), hinge_b], axis=1),
+                     "usp_abs_b": np.abs(s64 * d64).sum(axis=1), "pairs": pairs}
     # ---- the margins of every discrete choice (the generator's conditions) and the quantities whose float32 error they face
     two = np.sqrt(np.partition(d2, 1, axis=2)[:, :, :2])
     u = np.stack([utx, uty, usx, usy])
@@ -261,6 +278,43 @@ def keypoint_loss(tgt, src, hom, H, W, cell, weights=WEIGHTS, relax=RELAX, cross
     out.update(dscore_t=(dst * inner).reshape(B, 1, Hc, Wc), dshift_t=dshift_t.reshape(B, 2, Hc, Wc), dfeat_t=dfeat_t,
                dscore_s=(dss * inner).reshape(B, 1, Hc, Wc), dshift_s=dshift_s.reshape(B, 2, Hc, Wc), dfeat_s=dfeat_s)
     return out
+
+
+def conditions(r64, r32, exempt=None):
+    """-> None, or the reason the seed is refused: the oracle's margins (float64) against 100 x the float32 error of the
+    quantity each guards, element by element.  ``exempt``: {"a": bool [B, N], "neg": [bool [n] per pair]}: the placed ties,
+    whose own gap is 0 on purpose; no other choice is exempt."""
+    q64, q32, g = r64["q"], r32["q"], r64["gaps"]
+    exempt = exempt or {}
+    err_d = np.abs(q32["d"].astype(np.float64) - q64["d"])
+    err_w = np.abs(q32["w"].astype(np.float64) - q64["w"])
+    err_u = np.abs(q32["u"].astype(np.float64) - q64["u"])
+    gap_a = np.where(exempt["a"], np.inf, g["a"]) if "a" in exempt else g["a"]
+    checks = [("the gap behind a_i", gap_a, err_d), ("|d - 4|", g["valid"], err_d), ("d away from 0", g["dmin"], err_d),
+              ("a clamp end", g["clamp"], err_u)]
+    inner = np.isfinite(g["valid"][0])
+    for b in range(len(q64["dmat"])):
+        ew = err_w[:, b][:, inner]
+        pair = np.maximum(ew[0][:, None] + ew[0][None, :], ew[1][:, None] + ew[1][None, :])
+        gap_neg = np.where(exempt["neg"][b], np.inf, g["neg"][b]) if "neg" in exempt else g["neg"][b]
+        checks.append((f"a relax_field edge of pair {b}", g["relax"][b], pair))
+        checks.append((f"the negative's gap of pair {b}", gap_neg, np.abs(q32["dmat"][b].astype(np.float64) - q64["dmat"][b]).max(axis=1)))
+        checks.append((f"a hinge argument of pair {b}", g["hinge"][b], np.abs(q32["harg"][b].astype(np.float64) - q64["harg"][b])))
+    for what, gap, err in checks:
+        bad = ~(gap > 100.0 * err)
+        if bad.any():
+            k = np.unravel_index(int(np.argmax(bad)), bad.shape)
+            return f"{what}: {gap[k]:.3e} within 100 x its float32 error {err[k]:.3e}"
+    if (r64["M"], r64["hits"]) != (r32["M"], r32["hits"]) or not np.array_equal(r64["a"][r64["valid"]], r32["a"][r64["valid"]]):
+        return "the float32 oracle run decides differently"
+    return None
+
+
+def norm_back(g, x, s, eps=1e-8):
+    """Back through y = x / (|x + eps| + eps), per column: g, x [C, n], s [n] = |x + eps|."""
+    eps = g.dtype.type(eps)
+    D = s + eps
+    return g / D - (g * x).sum(0) / (D * D * s) * (x + eps)
 
 
 # ---- the trainer -------------------------------------------------------------------------------------------------------------

@@ -121,33 +121,6 @@ def consistency(tgt, src, hom, H, W, cell, net, loss_mod, dtype):
         return float(torch.nn.functional.mse_loss(res[mask], s["score"][mask]) * 2) if mask.any() else 0.0
 
 
-def conditions(r64, r32):
-    """-> None, or the reason the seed is refused: the oracle's margins (float64) against 100 x the float32 error of the
-    quantity each guards, element by element."""
-    q64, q32, g = r64["q"], r32["q"], r64["gaps"]
-    err_d = np.abs(q32["d"].astype(np.float64) - q64["d"])
-    err_w = np.abs(q32["w"].astype(np.float64) - q64["w"])
-    err_u = np.abs(q32["u"].astype(np.float64) - q64["u"])
-    checks = [("the gap behind a_i", g["a"], err_d), ("|d - 4|", g["valid"], err_d), ("d away from 0", g["dmin"], err_d),
-              ("a clamp end", g["clamp"], err_u)]
-    B = q64["d"].shape[0]
-    inner = np.isfinite(g["valid"][0])
-    for b in range(len(q64["dmat"])):
-        ew = err_w[:, b][:, inner]
-        pair = np.maximum(ew[0][:, None] + ew[0][None, :], ew[1][:, None] + ew[1][None, :])
-        checks.append((f"a relax_field edge of pair {b}", g["relax"][b], pair))
-        checks.append((f"the negative's gap of pair {b}", g["neg"][b], np.abs(q32["dmat"][b].astype(np.float64) - q64["dmat"][b]).max(axis=1)))
-        checks.append((f"a hinge argument of pair {b}", g["hinge"][b], np.abs(q32["harg"][b].astype(np.float64) - q64["harg"][b])))
-    for what, gap, err in checks:
-        bad = ~(gap > 100.0 * err)
-        if bad.any():
-            k = np.unravel_index(int(np.argmax(bad)), bad.shape)
-            return f"{what}: {gap[k]:.3e} within 100 x its float32 error {err[k]:.3e}"
-    if (r64["M"], r64["hits"]) != (r32["M"], r32["hits"]) or not np.array_equal(r64["a"][r64["valid"]], r32["a"][r64["valid"]]):
-        return "the float32 oracle run decides differently"
-    return None
-
-
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reference", default=os.environ.get("KP2D_REFERENCE"), help="a checkout of the reference project")
@@ -191,7 +164,7 @@ def main():
             inp = kr.make_loss_inputs(name, seed)
             call = (inp["tgt"], inp["src"], inp["hom"], inp["H"], inp["W"], inp["cell"], inp["weights"])
             o64, o32 = kr.keypoint_loss(*call), kr.keypoint_loss(*call, dtype=np.float32, grads=False)
-            why = conditions(o64, o32)
+            why = kr.conditions(o64, o32)
             if why is None:
                 r64, r32 = run_loss(inp, torch.float64), run_loss(inp, torch.float32)
                 if r64["recall"] != r32["recall"]:
@@ -294,7 +267,7 @@ def main():
             B = inp["B"]
             call = ({k: f64[k][:B] for k in ("score", "shift", "feat")}, {k: f64[k][B:] for k in ("score", "shift", "feat")},
                     inp["hom"], inp["H"], inp["W"], inp["cell"], inp["weights"])
-            why = why or conditions(kr.keypoint_loss(*call, grads=False), kr.keypoint_loss(*call, dtype=np.float32, grads=False))
+            why = why or kr.conditions(kr.keypoint_loss(*call, grads=False), kr.keypoint_loss(*call, dtype=np.float32, grads=False))
         if why is None and runs[torch.float64][2][2] != runs[torch.float32][2][2]:
             why = "the reference's float32 run gives another recall"
         if why is None:
