@@ -849,6 +849,101 @@ int kp2d_keypoint_loss(const float* score_t, const float* shift_t, const float* 
                        float* dfeat_t, float* dscore_s, float* dshift_s, float* dfeat_s, int64_t* counts, void* scratch,
                        size_t scratch_bytes, void* stream);
 
+/* ---- View pairs: homography sampling, image warp, cross-view depth (nano-vs-slam_amd/csrc/augment.hip) ----
+ * What the reference's dataset transforms do to make the second view of a training pair (src/data/dataset_utils.py:9-136 and
+ * :198-266, nyuv2.py:183-257): sample_homography, then tgm.HomographyWarper(im_h, im_w, mode="nearest") on the image, the
+ * labels and the depth, then a nearest Resize of the targets to 1 / d_f; and the one loss term that needs the warp, the
+ * depth head's MSE(depth_aug, warp(depth, H)) (KeypointNetwithIOLoss.py:587-603).  Stateless like the calls above:
+ * caller-owned device buffers, the caller's stream, no synchronisation, no host round trip, no float atomics; every argument
+ * is checked on the host before the first launch; every output is fully written.
+ *
+ * THE COORDINATE MAP.  One definition, used by kp2d_warp, kp2d_warp_backward, kp2d_cross_view_mse and the numpy oracle
+ * (tests/augment_ref.py).  Source map H x W (both >= 2), output Ho x Wo with stride s (Ho s == H, Wo s == W, else
+ * KP2D_ERR_ARG; s = 1 is the plain warp).  For the output pixel (i, j) and the frame's homography h (row-major [3,3]):
+ *       X = j s,  Y = i s                  (the pixel of the full-size grid that the reference's nearest Resize keeps)
+ *       gx = 2 X / (W - 1) - 1,   gy = 2 Y / (H - 1) - 1
+ *       u' = (h00 gx + h01 gy) + h02,   v' = (h10 gx + h11 gy) + h12,   w' = (h20 gx + h21 gy) + h22
+ *       px = ((u' / w' + 1) / 2) (W - 1),   py = ((v' / w' + 1) / 2) (H - 1)
+ *   all in IEEE double, the operations in the order written, none fused.  hom is [N,3,3] float32 (hom_f64 = 0; an entry is
+ *   converted exactly) or float64 (hom_f64 = 1).  This is grid_sample(x, H grid, align_corners=True): warp(x, H)(q) = x(H q) in
+ *   normalised coordinates, the convention of kp2d_keypoint_loss above (source = the augmented view).
+ *   NEAREST: xi = rint(px), yi = rint(py), ties to even (torch's nearbyint); the pixel is INSIDE iff 0 <= xi <= W - 1 and
+ *   0 <= yi <= H - 1; a non-finite coordinate is outside; an outside pixel gets fill.
+ *   BILINEAR (float32 sources only): x0 = floor(px), fx = px - x0, the same in y; the four weights (1 - fx)(1 - fy), fx (1 - fy),
+ *   (1 - fx) fy, fx fy are formed in double and rounded to fp32 once; a tap outside the map contributes zero whatever fill is
+ *   (torch's padding_mode="zeros"); the blend is fp32, unfused: ((w00 a + w01 b) + w10 c) + w11 d.
+ *
+ * kp2d_warp: src [N, C, H, W] of dtype KP2D_WARP_F32 / _U8 / _I32 / _I64 -> dst [N, C, Ho, Wo] of the same type; mode
+ *   KP2D_WARP_NEAREST or KP2D_WARP_BILINEAR (integer sources: nearest only, else KP2D_ERR_ARG); fill must be a value of the
+ *   source's type (an integer in its range; |fill| <= 2^53 for int64; not NaN for float32), else KP2D_ERR_ARG.  A thread per
+ *   output pixel, a workgroup per tile of KP2D_WARP_TILE_H rows x KP2D_WARP_TILE_W columns; the coordinates once, then the
+ *   channels.  Limits: 1 <= N <= 65535, C >= 1, H, W >= 2 (else KP2D_ERR_ARG); H, W <= 32768 and C <= 4096 (else
+ *   KP2D_ERR_UNSUPPORTED), so that C H W < 2^42 and every index is formed in 64 bits.
+ *
+ * kp2d_warp_backward: the gradient of the NEAREST warp.  dy [N, C, Ho, Wo] fp32 -> dx [N, C, H, W] fp32,
+ *       dx[n,c,p] = sum of dy[n,c,q] over the output pixels q, in ascending row-major order, whose nearest source pixel is p
+ *   (0 where there is none), the additions in fp32 in that order, no atomics: a thread per source pixel p maps the four
+ *   corners of [p - 1/2 - g, p + 1/2 + g]^2 (g = 1/64) through the frame's inverse homography (adjugate over determinant in
+ *   double), takes their bounding box in output pixels, widens it by one, clamps it, and tests every q of the box with the
+ *   forward's own coordinate function.  When a corner's inverse w' is <= 0 or not finite, or the matrix is singular or not
+ *   finite, that thread scans the WHOLE output: slow and correct.  Limits as kp2d_warp.  The bilinear warp has no backward.
+ *
+ * kp2d_homography_sample: the reference's sample_homography(shape = (H, W)), a thread per frame, all in double: the four
+ *   corners (+-1, +-1) scaled by patch_ratio (y also by hw_ratio = H / W); perspective offsets z0, z1 (x) and z2, z3 (y) times
+ *   amplitude / 2 (y: times hw_ratio), clipped to that; one scale about the centre; a translation inside the image; one of
+ *   the n_angles + 1 candidate angles (0, then linspace(-max_angle, max_angle, n_angles)) whose rotated corners stay inside
+ *   ([-1, 1) x [-hw_ratio, hw_ratio)); y / hw_ratio; the 8 x 8 system by elimination with partial pivoting (the reference's
+ *   pinv of a square non-singular matrix).  -> hom64 [B,3,3] float64 and hom32 [B,3,3] float32, its rounding (either may be
+ *   NULL, not both): it maps the first view's normalised coordinates to the second's, what kp2d_warp and the losses take.
+ *   The randomness enters through draws [B, KP2D_HOMOGRAPHY_DRAWS] float64, per frame
+ *       z0, z1, z2, z3    standard normals: the two x and the two y perspective offsets
+ *       u_s in [0,1)      idx = floor(u_s n_scales); idx = 0: scale 1; else the scale is 1 + z_s scaling_amplitude / 2, clipped
+ *       z_s               a standard normal (the reference draws n_scales of them and picks one; it never picks its last
+ *                         draw, valid = np.arange(n_scales): the same range here)
+ *       u_x, u_y in [0,1) the translation -t_min + u (t_max + t_min) per axis
+ *       u_r in [0,1)      the rotation valid[floor(u_r len(valid))]; no valid candidate (the reference raises): no rotation
+ *   so that the reference's own function, fed the same draws, pins the kernel.  perspective, scaling, rotation, translation
+ *   are switches (reference: all 1); reference defaults n_scales 100, n_angles 100, scaling_amplitude 0.2,
+ *   perspective_amplitude 0.2, patch_ratio 0.7, max_angle pi / 2.  B, H, W, n_scales >= 1, 1 <= n_angles <= 65536,
+ *   0 <= scaling_amplitude < 2, perspective_amplitude >= 0, 0 < patch_ratio <= 1, max_angle >= 0 (else KP2D_ERR_ARG).
+ * kp2d_homography_draws: fills draws from the library's own counter stream (not numpy's: a stated deviation, as in k-means,
+ *   mining and dropout).  With mix = splitmix64's finaliser (csrc/mix64.h):
+ *       h(slot, k) = mix(mix(mix(seed + 0x9E3779B97F4A7C15) ^ (step << 32 | frame)) ^ (slot << 32 | k)),  u(slot, k) = (h >> 11) 2^-53
+ *   a uniform slot (4, 6, 7, 8) is u(slot, 0); a normal slot (0..3, 5) is Box-Muller in double:
+ *   sqrt(-2 log(1 - u(slot, 0))) cos(2 pi u(slot, 1)).  B >= 1, 0 <= step < 2^32 (else KP2D_ERR_ARG).
+ *
+ * kp2d_cross_view_mse: depth, depth_aug [N, H, W] fp32 (after the sigmoid), hom as above.  The warp is nearest, at stride 1,
+ *   and an outside pixel is 0, as the reference's warper makes it:
+ *       diff = depth_aug - warp(depth, H)  (fp32);   loss = weight sum diff^2 / M;   M = N H W
+ *       d_depth_aug = weight 2 diff / M;   d_depth = warp_backward(-d_depth_aug)
+ *   *inside (int64) = the number of inside pixels.  inside_only = 1 restricts the sum, M (= *inside) and both gradients to the
+ *   inside pixels; M = 0 then gives loss 0 and zero gradients.  inside_only = 0 is the reference: an outside pixel pulls
+ *   depth_aug towards 0 (reproduced, not corrected).  The squares and their sum are float64: the N H W pixels (frame-major) in
+ *   chunks of 1024, a chunk a butterfly over the wave and the four waves in wave order, the chunks of a run (at most 1024
+ *   runs) in chunk order, the runs in run order; d_depth_aug = (float)((weight 2 / M) diff) with the product in double.
+ *   Bit-identical from run to run.  weight finite and >= 0; shapes as kp2d_warp with C = 1.
+ *   scratch: kp2d_cross_view_scratch_bytes(N, H W) bytes (0: bad shape), 16-byte aligned; a shorter one is KP2D_ERR_ARG. */
+#define KP2D_WARP_F32 0
+#define KP2D_WARP_U8 1
+#define KP2D_WARP_I32 2
+#define KP2D_WARP_I64 3
+#define KP2D_WARP_NEAREST 0
+#define KP2D_WARP_BILINEAR 1
+#define KP2D_WARP_TILE_W 64
+#define KP2D_WARP_TILE_H 4
+#define KP2D_HOMOGRAPHY_DRAWS 9
+int kp2d_homography_draws(double* draws, int B, uint64_t seed, int64_t step, void* stream);
+int kp2d_homography_sample(const double* draws, int B, int H, int W, int perspective, int scaling, int rotation, int translation,
+                           int n_scales, int n_angles, double scaling_amplitude, double perspective_amplitude, double patch_ratio,
+                           double max_angle, double* hom64, float* hom32, void* stream);
+int kp2d_warp(const void* src, int dtype, const void* hom, int hom_f64, int N, int C, int H, int W, int stride, int mode, double fill,
+              void* dst, void* stream);
+int kp2d_warp_backward(const float* dy, const void* hom, int hom_f64, int N, int C, int H, int W, int stride, float* dx, void* stream);
+size_t kp2d_cross_view_scratch_bytes(int N, int64_t HW);
+int kp2d_cross_view_mse(const float* depth, const float* depth_aug, const void* hom, int hom_f64, int N, int H, int W, double weight,
+                        int inside_only, float* loss, float* d_depth, float* d_depth_aug, int64_t* inside, void* scratch,
+                        size_t scratch_bytes, void* stream);
+
 /* ---- Keypoint scores: repeatability, localisation error, matching score (nano-vs-slam_amd/csrc/keypoint_metrics.hip) ----
  * The counts and sums behind the reference's compute_repeatability (src/evaluation/detector.py:67-113) and
  * compute_matching_score (src/evaluation/descriptor.py:112-170), for B image pairs per call.  Stateless like the calls

@@ -150,6 +150,12 @@ SIGNATURES = {
     "kp2d_depth_loss": (C.c_int, [_P, _P, C.c_int, C.c_int64, C.c_double, C.c_double] + [_P] * 5 + [_P, C.c_size_t, _P]),
     "kp2d_keypoint_loss_scratch_bytes": (C.c_size_t, [C.c_int] * 6),
     "kp2d_keypoint_loss": (C.c_int, [_P] * 7 + [C.c_int] * 9 + [C.c_double] * 6 + [_P] * 9 + [_P, C.c_size_t, _P]),
+    "kp2d_homography_draws": (C.c_int, [_P, C.c_int, C.c_uint64, C.c_int64, _P]),
+    "kp2d_homography_sample": (C.c_int, [_P] + [C.c_int] * 9 + [C.c_double] * 4 + [_P, _P, _P]),
+    "kp2d_warp": (C.c_int, [_P, C.c_int, _P] + [C.c_int] * 7 + [C.c_double, _P, _P]),
+    "kp2d_warp_backward": (C.c_int, [_P, _P] + [C.c_int] * 6 + [_P, _P]),
+    "kp2d_cross_view_scratch_bytes": (C.c_size_t, [C.c_int, C.c_int64]),
+    "kp2d_cross_view_mse": (C.c_int, [_P, _P, _P] + [C.c_int] * 4 + [C.c_double, C.c_int] + [_P] * 4 + [_P, C.c_size_t, _P]),
     "kp2d_seg_conf_lds_max": (C.c_int, []),
     "kp2d_seg_stats": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int64, C.c_int, C.c_int64, _P, _P, _P, _P, _P]),
     "kp2d_depth_scratch_bytes": (C.c_size_t, [C.c_int, C.c_int64]),

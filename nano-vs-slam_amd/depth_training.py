@@ -11,9 +11,10 @@ and csrc/vpr_head_train.hip (include/kp2d.h).
 
 Conventions kept from the reference: SILog's constants 10 and 0.15 and torch's unbiased variance, Huber's delta 1 and mean
 reduction, ``huber_loss_factor`` 1.0, the mask ``gt > 0``, ``torch.optim.Adam``'s update, the parameters' registration order,
-exact fp32 arithmetic.  The outer ``depth_loss`` weight 0.5 and the sum over the plain and the augmented view are the
-caller's.  Frozen: the backbone and every other head.  Not built: the reference's cross-view term
-``MSE(depth_aug, warp(depth, H)) * 0.5`` (there is no homography image warp here).  Deviations: the head runs as
+exact fp32 arithmetic.  The outer ``depth_loss`` weight 0.5 is the caller's; ``step`` / ``step_features`` take one view, and
+``step_pair`` / ``step_pair_features`` / ``pair_gradients`` take the plain and the augmented view with the reference's
+cross-view term ``MSE(depth_aug, warp(depth, H)) * 0.5`` (KeypointNetwithIOLoss.py:587-603; the warp is ``augment``'s).
+Frozen: the backbone and every other head.  Deviations: the head runs as
 ``depth_head.eval()`` under autograd (BatchNorm on its running statistics, no ``Dropout2d``); the loss is formed from the
 logits, so it stays finite where torch's ``log(sigmoid(z))`` is ``-inf``; no valid pixel gives loss 0 and a zero gradient
 (torch: NaN); one valid pixel gives Huber alone (torch: NaN); ``Dg = 0`` gives a zero SILog gradient (torch: NaN); a pixel
@@ -118,6 +119,7 @@ class DepthHeadTrainer(_DenseHeadTrainer):
             raise ValueError(f"DepthHeadTrainer: silog_weight {silog_weight} and huber_weight {huber_weight} must be finite and >= 0")
         self.silog_weight, self.huber_weight = float(silog_weight), float(huber_weight)
         self.parts = None       # float32 device tensor [SILog, Huber] of the last step, unweighted
+        self.pair_parts = self.inside = None      # of the last pair step: [SILog, Huber, SILog_aug, Huber_aug, cross]; inside pixels
 
     def _check_target(self, gt, shape, device):
         return _check_gt("DepthHeadTrainer", gt, shape, device)
@@ -125,3 +127,73 @@ class DepthHeadTrainer(_DenseHeadTrainer):
     def _loss(self, logits, gt):
         loss, dz, self.valid, self.stray, self.parts = depth_loss(logits, gt, self.silog_weight, self.huber_weight, return_parts=True)
         return loss, dz
+
+    # ---- the pair step: both views and the cross-view term ------------------------------------------------------------------
+    def pair_gradients(self, maps, maps_aug, gt, gt_aug, homography, cross_weight=0.5, inside_only=False):
+        """The reference's depth loss over a view pair (KeypointNetwithIOLoss.py:587-603), without an update:
+
+            L(z, gt) + L(z_aug, gt_aug) + cross_weight · MSE(sigmoid(z_aug), warp(sigmoid(z), homography))
+
+        ``maps`` = (x, skip) of the plain view and ``maps_aug`` of the augmented one ("last" mode: (feat, None)), each of N
+        frames; both go through the head as one batch of 2 N.  ``gt``, ``gt_aug`` at the logits' size; ``homography``
+        [N, 3, 3] float32 or float64 in normalised coordinates, as ``augment.view_pair`` returns it.  L is ``depth_loss``,
+        once per view (each view has its own SILog statistics); the cross term is ``augment.cross_view_mse`` on the two
+        sigmoids (nearest warp, outside pixels 0; ``inside_only`` as there), its gradients chained through p (1 - p) and
+        added to the logits' -> (loss, logits [2 N, 1, Hs, Ws], the gradients in ``parameters()`` order).  Afterwards
+        ``pair_parts`` is float32 [SILog, Huber, SILog_aug, Huber_aug, cross] (unweighted; cross is the MSE), ``inside`` the
+        int64 count of inside pixels, ``valid`` and ``stray`` the two views' sums, ``parts`` the plain view's."""
+        from .augment import cross_view_mse
+        who = "DepthHeadTrainer.pair_gradients"
+        (x, skip), (xa, skipa) = maps, maps_aug
+        for a, b in ((x, xa), (skip, skipa)):
+            if (a is None) != (b is None) or (a is not None and (not isinstance(a, torch.Tensor) or not isinstance(b, torch.Tensor) or
+                                                                 a.shape != b.shape or a.device != b.device)):
+                raise ValueError(f"{who}: the two views' maps must have one shape and one device")
+        cross_weight = float(cross_weight)
+        if not (0.0 <= cross_weight < float("inf")):
+            raise ValueError(f"{who}: cross_weight must be finite and >= 0, got {cross_weight}")
+        N = x.shape[0]
+        for name, g in (("gt", gt), ("gt_aug", gt_aug)):
+            if not isinstance(g, torch.Tensor) or not _ops._is_device(g) or g.dim() not in (3, 4) or g.shape[0] != N:
+                raise ValueError(f"{who}: {name} must be a device tensor [N, Hs, Ws] or [N, 1, Hs, Ws] of the {N} frames")
+        if gt.shape != gt_aug.shape:
+            raise ValueError(f"{who}: gt {tuple(gt.shape)} and gt_aug {tuple(gt_aug.shape)} must have one shape")
+
+        def pair_loss(logits, target):
+            z, za = logits[:N], logits[N:]
+            l0, dz0, v0, s0, p0 = depth_loss(z, target[:N], self.silog_weight, self.huber_weight, return_parts=True)
+            l1, dz1, v1, s1, p1 = depth_loss(za, target[N:], self.silog_weight, self.huber_weight, return_parts=True)
+            p, pa = torch.sigmoid(z), torch.sigmoid(za)
+            mse, dp, dpa, self.inside = cross_view_mse(p, pa, homography, weight=1.0, inside_only=inside_only)
+            dz = torch.cat([dz0 + cross_weight * dp * (p * (1.0 - p)), dz1 + cross_weight * dpa * (pa * (1.0 - pa))])
+            self.valid, self.stray, self.parts = v0 + v1, s0 + s1, p0
+            self.pair_parts = torch.cat([p0, p1, mse.reshape(1)])
+            return (l0 + l1) + cross_weight * mse, dz
+
+        both = lambda a, b: None if a is None else torch.cat([a, b])
+        return self.gradients(both(x, xa), both(skip, skipa), torch.cat([gt, gt_aug]), loss_fn=pair_loss)
+
+    def step_pair_features(self, maps, maps_aug, gt, gt_aug, homography, cross_weight=0.5, inside_only=False):
+        """``pair_gradients`` and one Adam update (one step, one version bump per parameter) -> the loss before the update."""
+        loss, _, grads = self.pair_gradients(maps, maps_aug, gt, gt_aug, homography, cross_weight, inside_only)
+        self._apply(self.parameters(), grads)
+        return loss
+
+    def step_pair(self, frames, frames_aug, gt, gt_aug, homography, cross_weight=0.5, inside_only=False):
+        """Both views' frames [N, 3, H, W] (``augment.view_pair``'s image and image_aug) -> the loss before the update.  The
+        frozen backbone runs on the two views as one batch, as ``step`` runs it on one."""
+        for name, f in (("frames", frames), ("frames_aug", frames_aug)):
+            if not isinstance(f, torch.Tensor) or not _ops._is_device(f):
+                raise ValueError(f"DepthHeadTrainer.step_pair: {name} must be a device tensor (there is no CPU path)")
+        if frames.shape != frames_aug.shape:
+            raise ValueError(f"DepthHeadTrainer.step_pair: frames {tuple(frames.shape)} and frames_aug {tuple(frames_aug.shape)} differ")
+        N = frames.shape[0]
+        both = torch.cat([frames, frames_aug])
+        with torch.no_grad():
+            if self.train == "head":
+                x, skip = self.model.backbone_maps(both)
+                return self.step_pair_features((x[:N], skip[:N]), (x[N:], skip[N:]), gt, gt_aug, homography, cross_weight, inside_only)
+            half = self.model.cell // 2
+            shape = (self.convs[-1].weight.shape[1], both.shape[2] // half, both.shape[3] // half)
+            _, feat = self.model.forward_with_tap(both, f"{self._ATTR}.convs.{len(self.convs) - 2}", shape)
+        return self.step_pair_features((feat[:N], None), (feat[N:], None), gt, gt_aug, homography, cross_weight, inside_only)

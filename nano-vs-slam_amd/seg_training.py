@@ -212,15 +212,16 @@ class _DenseHeadTrainer(AdamTrainer):
         self._check_maps(x, skip)
         return self._forward(x, skip)[0]
 
-    def gradients(self, x, skip, target):
-        """One forward, loss and backward without an update -> (loss, logits, the gradients in ``parameters()`` order)."""
+    def gradients(self, x, skip, target, loss_fn=None):
+        """One forward, loss and backward without an update -> (loss, logits, the gradients in ``parameters()`` order).
+        ``loss_fn(logits, target) -> (loss, dlogits)`` stands in for the trainer's own loss (the depth trainer's pair step)."""
         self._check_maps(x, skip)
         params = self.parameters()
         self._check_contiguous(params, "the head's")
         Hs, Ws = (x.shape[2], x.shape[3]) if self.train == "last" else (skip.shape[2], skip.shape[3])
         target = self._check_target(target, (x.shape[0], Hs, Ws), x.device)
         logits, a = self._forward(x, skip)
-        loss, dz = self._loss(logits, target)
+        loss, dz = (loss_fn or self._loss)(logits, target)
         last = self.convs[-1]
         head = self.train == "head"
         dw, db, dy = conv_bias_backward(a["feat"], last.weight, dz, need_dx=head)
