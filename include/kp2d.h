@@ -944,6 +944,72 @@ int kp2d_cross_view_mse(const float* depth, const float* depth_aug, const void* 
                         int inside_only, float* loss, float* d_depth, float* d_depth_aug, int64_t* inside, void* scratch,
                         size_t scratch_bytes, void* stream);
 
+/* ---- Attention head training: the SegFormerAttentionModule's stages (nano-vs-slam_amd/csrc/attention_train.hip) ----
+ * What the V2 SegmentationHeadATT needs beside the calls above: its two SegFormerAttentionModule (modules/segformer.py:209-220)
+ * stage by stage, each with a forward that returns what its backward reads and a backward that returns every gradient.
+ * Stateless: caller-owned device buffers, the caller's stream, no synchronisation; every argument is checked before the first
+ * launch and every output is fully written.  Tensors are fp32 PLANAR [N, C, H, W]; 1 <= N <= 65535, H, W >= 1 (else
+ * KP2D_ERR_ARG); every channel count is 48, 64, 96 or 128 and H W <= 2^24 (else KP2D_ERR_UNSUPPORTED).  Exact fp32; the matrix
+ * products are chains of v_mfma_f32_16x16x4_f32 over the reduction index in ascending order (the attention logits: float64).  No float atomics: every sum's
+ * order is fixed by the shapes, so a call is bit-identical from run to run.
+ *   scratch: kp2d_att_train_scratch_bytes(N, H, W, Cin, Cout) bytes (0: bad shape), 16-byte aligned, of the call's own N, H, W
+ *   and channel counts (patch2: Cin = C, Cout = 2 C; one-count calls: Cin = Cout = C); a shorter one is KP2D_ERR_ARG.
+ *
+ * kp2d_layernorm_forward_train: the reference's channel LayerNorm (segformer.py:63-73, not nn.LayerNorm): per pixel
+ *   mean = sum_c x / C (channels in order), var = sum_c (x - mean)^2 / C, D = sqrt(var) + eps,
+ *   y = (x - mean) / D * g + b; g, b [C].  Saved per pixel: mean [N, H W] and rinv = 1 / D [N, H W].
+ * kp2d_layernorm_backward: with d = x - mean, s = sqrt(var) (formed again from x and the saved mean), D = s + eps, a = g dy:
+ *   dx = (a - mean_c a) / D - d (sum_c a d) / (C s D^2);  a pixel with s = 0 takes the second term as 0 (torch: NaN).
+ *   dg[c] = sum dy d rinv, db[c] = sum dy: per (frame, channel) plane thread t of 256 adds pixels t, t + 256, ... in order,
+ *   a wave's 64 partials by butterfly, the four waves as (0 + 1) + (2 + 3); then the frames in frame order.
+ * kp2d_pointwise_forward_train: y = conv1x1(x, w) (+ bias), w [Cout, Cin], bias [Cout] or NULL.  gelu != 0: pre receives that
+ *   value and y = pre / 2 (1 + erf(pre / sqrt 2)) (nn.GELU()'s default, erff); otherwise pre may be NULL.
+ * kp2d_gelu_backward: dpre = dy (Phi(pre) + pre phi(pre)), n elements.
+ * kp2d_pointwise_backward: dy [N, Cout, H, W] -> dx [N, Cin, H, W] (NULL: not formed), d_weight [Cout, Cin], d_bias [Cout]
+ *   (NULL: not formed; summed as db above).  d_weight: the N H W pixels in (frame, pixel) order are cut into at most 128 slabs
+ *   of max(64, ceil(N H W / 128) rounded up to 4) pixels; a slab's partial is one chain over its pixels; the partials are added
+ *   in slab order.
+ * kp2d_patch2_forward_train: to_kv, a 2 x 2 stride-2 convolution without padding or bias, w [2 C, C, 2, 2], C in {48, 64},
+ *   H, W >= 2: y [N, 2 C, H / 2, W / 2] (floor); the reduction index is 4 ci + 2 a + b.
+ * kp2d_patch2_backward: dy [N, 2 C, H / 2, W / 2] -> dx [N, C, H, W] (NULL: not formed), d_weight as above over the patches.
+ *   On an odd map the last row or column is in no patch: its dx is written as exact zeros.
+ * kp2d_dwconv3_forward_train / _backward: depthwise 3 x 3, padding 1, bias: w [C, 1, 3, 3], taps in row-major order;
+ *   dx [N, C, H, W] (NULL: not formed), d_weight [C, 1, 3, 3] and d_bias [C] summed per plane and then per frame as db above.
+ * kp2d_attention_forward_train: 4 heads of dimension C / 4 (C in {48, 64}); q [N, C, H, W], head h owns channels h C/4 ...;
+ *   kv [N, 2 C, H / 2, W / 2], keys in the first C channels, values in the second; S = H W queries, T = (H/2)(W/2) keys,
+ *   H, W >= 2.  o [N, C, H, W] = softmax(scale q k^T) v with scale = (C / 4)^-0.5, by an online softmax over
+ *   key tiles of 16 in ascending order; lse [2, N, 4, S]: lse[0] = max + log(sum exp) of each query's scaled logits rounded
+ *   to fp32, lse[1] = (max - lse[0]) + log(sum exp), what that rounding dropped (near 60 an ulp is 4e-6, which every
+ *   probability the backward forms again would carry).  Nothing of size S x T is stored; saturated rows stay finite (every
+ *   exponent is <= 0).  The logits alone are formed in float64 (v_mfma_f64_16x16x4_f64 on the widened fp32 operands, scale
+ *   = (C / 4)^-0.5 in double), with the running maximum and the log-sum-exp: an ulp of a float32 logit near 60 is 3.8e-6, which
+ *   every probability the backward forms again would carry (measured with fp32 logits: dK, dV at 1.3 to 1.5 x 16 * 2^-24).
+ *   Only the exponent's argument, logit - max or logit - lse, is rounded to fp32; the same function forms the logits in the
+ *   forward and in both backward kernels.
+ * kp2d_attention_backward: P = exp((scale q k^T - lse[0]) - lse[1]) again; delta = sum_c dO O; dV = P^T dO; dS = P (dO V^T - delta);
+ *   dq = scale dS K [N, C, H, W]; dkv [N, 2 C, H / 2, W / 2] = (scale dS^T Q, dV).  dq belongs to tiles of 16 queries, which
+ *   walk the keys in ascending order; dK and dV belong to tiles of 16 keys, which walk the queries in ascending order.  delta
+ *   is the same chain over c as dO V^T, so with one key (P = 1, O = V) dS, dq and dK are exact zeros. */
+size_t kp2d_att_train_scratch_bytes(int N, int H, int W, int Cin, int Cout);
+int kp2d_layernorm_forward_train(const float* x, const float* g, const float* b, int N, int C, int H, int W, double eps, float* y,
+                                 float* mean, float* rinv, void* stream);
+int kp2d_layernorm_backward(const float* x, const float* g, const float* mean, const float* rinv, const float* dy, int N, int C, int H,
+                            int W, double eps, float* dx, float* dg, float* db, void* scratch, size_t scratch_bytes, void* stream);
+int kp2d_pointwise_forward_train(const float* x, const float* w, const float* bias, int N, int H, int W, int Cin, int Cout, int gelu,
+                                 float* y, float* pre, void* stream);
+int kp2d_gelu_backward(const float* pre, const float* dy, int64_t n, float* dpre, void* stream);
+int kp2d_pointwise_backward(const float* x, const float* w, const float* dy, int N, int H, int W, int Cin, int Cout, float* dx,
+                            float* d_weight, float* d_bias, void* scratch, size_t scratch_bytes, void* stream);
+int kp2d_patch2_forward_train(const float* x, const float* w, int N, int C, int H, int W, float* y, void* stream);
+int kp2d_patch2_backward(const float* x, const float* w, const float* dy, int N, int C, int H, int W, float* dx, float* d_weight,
+                         void* scratch, size_t scratch_bytes, void* stream);
+int kp2d_dwconv3_forward_train(const float* x, const float* w, const float* bias, int N, int C, int H, int W, float* y, void* stream);
+int kp2d_dwconv3_backward(const float* x, const float* w, const float* dy, int N, int C, int H, int W, float* dx, float* d_weight,
+                          float* d_bias, void* scratch, size_t scratch_bytes, void* stream);
+int kp2d_attention_forward_train(const float* q, const float* kv, int N, int C, int H, int W, float* o, float* lse, void* stream);
+int kp2d_attention_backward(const float* q, const float* kv, const float* o, const float* lse, const float* d_o, int N, int C, int H, int W,
+                            float* dq, float* dkv, void* scratch, size_t scratch_bytes, void* stream);
+
 /* ---- Keypoint scores: repeatability, localisation error, matching score (nano-vs-slam_amd/csrc/keypoint_metrics.hip) ----
  * The counts and sums behind the reference's compute_repeatability (src/evaluation/detector.py:67-113) and
  * compute_matching_score (src/evaluation/descriptor.py:112-170), for B image pairs per call.  Stateless like the calls

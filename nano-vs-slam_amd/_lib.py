@@ -156,6 +156,18 @@ SIGNATURES = {
     "kp2d_warp_backward": (C.c_int, [_P, _P] + [C.c_int] * 6 + [_P, _P]),
     "kp2d_cross_view_scratch_bytes": (C.c_size_t, [C.c_int, C.c_int64]),
     "kp2d_cross_view_mse": (C.c_int, [_P, _P, _P] + [C.c_int] * 4 + [C.c_double, C.c_int] + [_P] * 4 + [_P, C.c_size_t, _P]),
+    "kp2d_att_train_scratch_bytes": (C.c_size_t, [C.c_int] * 5),
+    "kp2d_layernorm_forward_train": (C.c_int, [_P] * 3 + [C.c_int] * 4 + [C.c_double] + [_P] * 3 + [_P]),
+    "kp2d_layernorm_backward": (C.c_int, [_P] * 5 + [C.c_int] * 4 + [C.c_double] + [_P] * 3 + [_P, C.c_size_t, _P]),
+    "kp2d_pointwise_forward_train": (C.c_int, [_P] * 3 + [C.c_int] * 6 + [_P, _P, _P]),
+    "kp2d_gelu_backward": (C.c_int, [_P, _P, C.c_int64, _P, _P]),
+    "kp2d_pointwise_backward": (C.c_int, [_P] * 3 + [C.c_int] * 5 + [_P] * 3 + [_P, C.c_size_t, _P]),
+    "kp2d_patch2_forward_train": (C.c_int, [_P, _P] + [C.c_int] * 4 + [_P, _P]),
+    "kp2d_patch2_backward": (C.c_int, [_P] * 3 + [C.c_int] * 4 + [_P, _P] + [_P, C.c_size_t, _P]),
+    "kp2d_dwconv3_forward_train": (C.c_int, [_P] * 3 + [C.c_int] * 4 + [_P, _P]),
+    "kp2d_dwconv3_backward": (C.c_int, [_P] * 3 + [C.c_int] * 4 + [_P] * 3 + [_P, C.c_size_t, _P]),
+    "kp2d_attention_forward_train": (C.c_int, [_P, _P] + [C.c_int] * 4 + [_P, _P, _P]),
+    "kp2d_attention_backward": (C.c_int, [_P] * 5 + [C.c_int] * 4 + [_P, _P] + [_P, C.c_size_t, _P]),
     "kp2d_seg_conf_lds_max": (C.c_int, []),
     "kp2d_seg_stats": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int64, C.c_int, C.c_int64, _P, _P, _P, _P, _P]),
     "kp2d_depth_scratch_bytes": (C.c_size_t, [C.c_int, C.c_int64]),

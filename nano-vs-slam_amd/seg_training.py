@@ -79,8 +79,9 @@ def segmentation_loss(logits, labels, ce_weight=0.5, dice_weight=1.5, ignore_ind
     return loss, dz, counts[0], counts[1]
 
 
-def _check_head(model, train, who="SegHeadTrainer", attr="seg_head", no_head=None):
-    """The refusals of a dense head's trainer (``who``, on ``model.<attr>``), each with its reason -> the head's layers."""
+def _check_head(model, train, who="SegHeadTrainer", attr="seg_head", no_head=None, attention_walk=False):
+    """The refusals of a dense head's trainer (``who``, on ``model.<attr>``), each with its reason -> the head's layers.
+    ``attention_walk``: the trainer is one of ``attention_training``'s, which take the attention head and nothing else."""
     if train not in ("head", "last"):
         raise ValueError(f"{who}: train must be 'head' or 'last', got {train!r}")
     head = getattr(model, attr, None)
@@ -91,9 +92,12 @@ def _check_head(model, train, who="SegHeadTrainer", attr="seg_head", no_head=Non
     if getattr(model, "upscale_method", "pixelshuffle") != "pixelshuffle" or hasattr(head, "upsample"):
         raise ValueError(f"{who}: upscale_method='convtranspose' (to_mcu) is not supported: only pixel shuffle has a backward")
     attention = bool(getattr(model, "use_attention", False))
-    if attention and train == "head":
-        raise ValueError(f"{who}: train='head' on an attention head is not supported (no attention backward exists); "
-                         "train='last' is")
+    if attention_walk and not attention:
+        raise ValueError(f"{who}: the model has no attention head (use_attention is off): its head is "
+                         f"{'DepthHeadTrainer' if attr == 'depth_head' else 'SegHeadTrainer'}'s")
+    if attention and train == "head" and not attention_walk:
+        raise ValueError(f"{who}: train='head' on an attention head is not supported (no attention backward exists in this "
+                         f"trainer: attention_training.Attention{who} has it); train='last' is")
     convs = list(head.convs)
     if len(convs) != (8 if attention else 9):
         raise ValueError(f"{who}: unexpected head of {len(convs)} layers")
@@ -106,13 +110,19 @@ def _check_head(model, train, who="SegHeadTrainer", attr="seg_head", no_head=Non
                          f"needs Cin % 16 == 0, {MIN_CH} <= Cin <= {MAX_CH}, 1 <= Cout <= {MAX_CH}")
     if train == "head":
         for i, layer in enumerate(convs[:-1]):
+            if attention and i in (1, 2):
+                c = layer.att.fn.to_q.weight.shape[0]
+                if c not in (48, 64):
+                    raise ValueError(f"{who}: {attr}.convs.{i} is an attention module of {c} channels; the attention kernels take 48 or 64")
+                continue
             co, ci = layer.conv.weight.shape[:2]
             if ci % 16 or co % 16 or not (MIN_CH <= ci <= MAX_CH and MIN_CH <= co <= MAX_CH):
                 raise ValueError(f"{who}: {attr}.convs.{i} has channel counts {ci} -> {co}, which the conv kernels do not take "
                                  f"(C % 16 == 0, {MIN_CH} <= C <= {MAX_CH}); train='last' does not run this layer")
-        c_in, c_hidden, d1 = convs[0].conv.weight.shape[1], convs[0].conv.weight.shape[0], convs[4].conv.weight.shape[0]
-        if d1 % 4 or convs[5].conv.weight.shape[1] != d1 // 4 + c_in or convs[6].conv.weight.shape[0] % 4 \
-                or convs[7].conv.weight.shape[1] <= convs[6].conv.weight.shape[0] // 4:
+        k = 3 if attention else 4       # the layer before the first pixel shuffle
+        c_in, c_hidden, d1 = convs[0].conv.weight.shape[1], convs[0].conv.weight.shape[0], convs[k].conv.weight.shape[0]
+        if d1 % 4 or convs[k + 1].conv.weight.shape[1] != d1 // 4 + c_in or convs[k + 2].conv.weight.shape[0] % 4 \
+                or convs[k + 3].conv.weight.shape[1] <= convs[k + 2].conv.weight.shape[0] // 4:
             raise ValueError(f"{who}: the head's channel counts (c_in {c_in}, c_hidden {c_hidden}, d1 {d1}) do not chain")
     return convs
 
@@ -124,9 +134,10 @@ class _DenseHeadTrainer(AdamTrainer):
     (``_TARGET``), and supplies ``_check_target`` and ``_loss``."""
 
     _WHO = _ATTR = None
+    _ATTENTION = False      # attention_training's trainers: the V2 SegmentationHeadATT's walk
 
     def _init_walk(self, model, lr, train, betas, eps, no_head=None):
-        self.convs = _check_head(model, train, self._WHO, self._ATTR, no_head)
+        self.convs = _check_head(model, train, self._WHO, self._ATTR, no_head, attention_walk=self._ATTENTION)
         self._init_adam(lr, betas, eps)
         self.model, self.train = model, train
         self.slope = LEAKY_SLOPE if getattr(model, "leaky_relu", True) else 0.0
@@ -141,11 +152,12 @@ class _DenseHeadTrainer(AdamTrainer):
         raise NotImplementedError
 
     def parameters(self):
-        """The trained parameters in the reference's registration order: 26 in "head" mode, 2 in "last" mode."""
+        """The trained parameters in the reference's registration order: 26 in "head" mode (47 on the attention head), 2 in
+        "last" mode."""
         out = []
         if self.train == "head":
             for layer in self.convs[:-1]:
-                out += [layer.conv.weight, layer.bn.weight, layer.bn.bias]
+                out += _ops.attention_module_parameters(layer) if hasattr(layer, "att") else [layer.conv.weight, layer.bn.weight, layer.bn.bias]
         return out + [self.convs[-1].weight, self.convs[-1].bias]
 
     # ---- shapes ----------------------------------------------------------------------------------------------------------
@@ -162,19 +174,21 @@ class _DenseHeadTrainer(AdamTrainer):
             raise ValueError(f"{who}: train='head' needs both backbone maps (model.backbone_maps)")
         _ops._f32_maps(who, (("x", x), ("skip", skip)))
         c_in = self.convs[0].conv.weight.shape[1]
-        c_skip = self.convs[7].conv.weight.shape[1] - self.convs[6].conv.weight.shape[0] // 4
+        c_skip = self.convs[-2].conv.weight.shape[1] - self.convs[-3].conv.weight.shape[0] // 4
         N, _, H, W = x.shape
         if H % 2 or W % 2:
             raise ValueError(f"{who}: the backbone map must have even height and width, got {H} x {W} "
                              "(the pooled and shuffled map would not concatenate with it; the reference's own cat fails there)")
         if x.shape[1] != c_in or tuple(skip.shape) != (N, c_skip, 2 * H, 2 * W):
             raise ValueError(f"{who}: needs x [N, {c_in}, H, W] and skip [N, {c_skip}, 2 H, 2 W], got {tuple(x.shape)}, {tuple(skip.shape)}")
+        if self._ATTENTION and (H < 4 or W < 4):
+            raise ValueError(f"{who}: the backbone map must be at least 4 x 4, got {H} x {W} (the pooled map needs one 2 x 2 key patch)")
 
     def _scratch(self, x, skip):
         """One buffer for every cbr call of the walk: the largest layer at the largest map."""
         lib = _lib.load()
         N = x.shape[0]
-        cmax = max(max(l.conv.weight.shape[:2]) for l in self.convs[:-1])
+        cmax = max(max(l.conv.weight.shape[:2]) for l in self.convs[:-1] if hasattr(l, "conv"))
         nbytes = int(lib.kp2d_cbr_train_scratch_bytes(N, skip.shape[2], skip.shape[3], cmax, cmax))
         if nbytes == 0:
             raise ValueError(f"{self._WHO}: maps {tuple(x.shape)}, {tuple(skip.shape)} are not supported")
@@ -193,6 +207,8 @@ class _DenseHeadTrainer(AdamTrainer):
         def cbr(i, x):
             return cbr_layer_forward(self.convs[i], x, self.slope, scratch)
 
+        if self._ATTENTION:
+            return self._forward_attention(x, skip, scratch, cbr)
         a[0] = cbr(0, x)
         a[1] = cbr(1, a[0][1])
         pooled = maxpool2_forward(a[1][1])
@@ -205,6 +221,32 @@ class _DenseHeadTrainer(AdamTrainer):
         feat = a[7][1]
         a["feat"], a["scratch"] = feat, scratch
         return conv_bias_forward(feat, last.weight, last.bias), a
+
+    def _forward_attention(self, x, skip, scratch, cbr):
+        """The V2 SegmentationHeadATT: convs[1] and convs[2] are attention modules, one before and one after the pooling."""
+        last = self.convs[-1]
+        a = {}
+        a[0] = cbr(0, x)
+        y1, a[1] = _ops.attention_module_forward(self.convs[1], a[0][1])
+        y2, a[2] = _ops.attention_module_forward(self.convs[2], maxpool2_forward(y1))
+        a["pool_in"] = y1
+        a[3] = cbr(3, y2)
+        a[4] = cbr(4, shuffle_cat_forward(a[3][1], x))
+        a[5] = cbr(5, a[4][1])
+        a[6] = cbr(6, shuffle_cat_forward(a[5][1], skip))
+        feat = a[6][1]
+        a["feat"], a["scratch"] = feat, scratch
+        return conv_bias_forward(feat, last.weight, last.bias), a
+
+    def _backward_attention(self, a, dy, grads, back):
+        """``back(i, dy)`` undoes Conv + BatchNorm layer i into grads[slot(i)]; the modules' 15 gradients go to 3 ... 32."""
+        dy = back(6, dy)
+        dy = back(5, shuffle_cat_backward(dy, self.convs[5].conv.weight.shape[0] // 4))
+        dy = back(4, dy)
+        dy = back(3, shuffle_cat_backward(dy, self.convs[3].conv.weight.shape[0] // 4))      # (x is a frozen backbone map: no gradient)
+        grads[18:33], dy = _ops.attention_module_backward(self.convs[2], a[2], dy)
+        grads[3:18], dy = _ops.attention_module_backward(self.convs[1], a[1], maxpool2_backward(a["pool_in"], dy))
+        back(0, dy, need_dx=False)                                                           # (the backbone is frozen: no dx)
 
     def forward_features(self, x, skip=None):
         """The head's training forward -> logits [N, classes, Hs, Ws].  "head" mode: the two backbone maps; "last" mode: the
@@ -227,13 +269,18 @@ class _DenseHeadTrainer(AdamTrainer):
         dw, db, dy = conv_bias_backward(a["feat"], last.weight, dz, need_dx=head)
         if not head:
             return loss, logits, [dw, db]
-        grads = [None] * 24 + [dw, db]
+        grads = [None] * (45 if self._ATTENTION else 24) + [dw, db]
         scratch = a["scratch"]
 
         def back(i, dy, need_dx=True):
             g = cbr_layer_backward(self.convs[i], a[i], dy, self.slope, need_dx=need_dx, scratch=scratch)
-            grads[3 * i:3 * i + 3] = g[:3]
+            at = 3 * i if not self._ATTENTION or i == 0 else 3 * i + 24      # (two modules of 15 tensors stand where two layers of 3 did)
+            grads[at:at + 3] = g[:3]
             return g[3]
+
+        if self._ATTENTION:
+            self._backward_attention(a, dy, grads, back)
+            return loss, logits, grads
 
         dy = back(7, dy)
         dy = back(6, shuffle_cat_backward(dy, self.convs[6].conv.weight.shape[0] // 4))

@@ -6,6 +6,8 @@
   ``cbr_layer_forward`` / ``cbr_layer_backward`` run one such layer of a model and undo it from what the forward kept.
 * ``conv_bias_forward`` / ``conv_bias_backward``, ``maxpool2_forward`` / ``maxpool2_backward``, ``shuffle_cat_forward`` /
   ``shuffle_cat_backward`` — a 3x3 convolution with bias and the dense heads' two scale changes (csrc/seg_train.hip).
+* ``layernorm_*``, ``pointwise_*``, ``patch2_*``, ``dwconv3_*``, ``attention_*`` and ``attention_module_forward`` /
+  ``attention_module_backward`` — the stages of the attention head's SegFormerAttentionModule (csrc/attention_train.hip).
 * ``adam_step`` (csrc/vlad_train.hip) and ``AdamTrainer``, the base of every trainer: settings, moments, the one update loop.
 
 The losses and the NetVLAD layer calls stay with their trainers.  The two styles of refusal stay as they were: the cbr calls and
@@ -396,3 +398,272 @@ def shuffle_cat_backward(dout, C):
     da = torch.empty(N, 4 * C, H // 2, W // 2, dtype=torch.float32, device=dout.device)
     _lib.check(_lib.load().kp2d_shuffle_cat_backward(_ptr(dout.contiguous()), N, C, Ct - C, H // 2, W // 2, _ptr(da), _stream(dout.device)))
     return da
+
+
+# ---- the attention head's SegFormerAttentionModule, stage by stage (csrc/attention_train.hip) -------------------------------
+ATT_CH = (48, 64, 96, 128)      # the channel counts the stage calls take
+ATT_HEADS = 4
+LN_EPS = 1e-5                   # the reference's LayerNorm(dim, eps=1e-5)
+
+
+def _check_att(where, maps, weights=(), vectors=(), attention=False):
+    """``maps``: (name, tensor, channels or None) float32 [N, C, H, W] of one N, H, W; ``weights``: (name, tensor, shape);
+    ``vectors``: (name, tensor, numel) -> (N, H, W).  Placement, dtype, contiguity, then shapes: all before any library call."""
+    _f32_maps(where, tuple((n, t) for n, t, _ in maps))
+    for name, t, _ in tuple(weights) + tuple(vectors):
+        if not isinstance(t, torch.Tensor) or not _is_device(t):
+            raise ValueError(f"{where}: {name} must be a device tensor (there is no CPU path)")
+        if t.dtype != torch.float32 or t.device != maps[0][1].device:
+            raise ValueError(f"{where}: {name} must be float32 on {maps[0][1].device}, got {t.dtype} on {t.device}")
+    for name, t in tuple((n, t) for n, t, _ in maps) + tuple((n, t) for n, t, _ in weights) + tuple((n, t) for n, t, _ in vectors):
+        if not t.is_contiguous():
+            raise ValueError(f"{where}: {name} must be contiguous")
+    N, _, H, W = maps[0][1].shape
+    if not (1 <= N <= 65535 and H >= 1 and W >= 1 and H * W <= 2 ** 24):
+        raise ValueError(f"{where}: needs 1 <= N <= 65535, H, W >= 1 and H W <= 2^24, got {tuple(maps[0][1].shape)}")
+    for name, t, c in maps:
+        if c is not None and t.shape[1] != c:
+            raise ValueError(f"{where}: {name} must have {c} channels, got {tuple(t.shape)}")
+        if t.shape[1] not in ATT_CH:
+            raise ValueError(f"{where}: {name} has {t.shape[1]} channels; the kernels take {ATT_CH}")
+    for name, t, shape in weights:
+        if tuple(t.shape) != tuple(shape):
+            raise ValueError(f"{where}: {name} must be {tuple(shape)}, got {tuple(t.shape)}")
+    for name, t, n in vectors:
+        if t.numel() != n:
+            raise ValueError(f"{where}: {name} must have {n} elements, got {tuple(t.shape)}")
+    if attention and (H < 2 or W < 2 or maps[0][1].shape[1] > 64):
+        raise ValueError(f"{where}: needs H, W >= 2 (one 2 x 2 key patch) and 48 or 64 channels, got {tuple(maps[0][1].shape)}")
+    return N, H, W
+
+
+def _att_channels(x):
+    """The channel count of a call's first map, which ``_check_att`` then checks in full."""
+    if not isinstance(x, torch.Tensor) or x.dim() != 4:
+        raise ValueError(f"the first argument must be a float32 device tensor [N, C, H, W], got {type(x).__name__} "
+                         f"{tuple(x.shape) if isinstance(x, torch.Tensor) else ''}")
+    return x.shape[1]
+
+
+def _same(where, name, t, shape):
+    if tuple(t.shape) != tuple(shape):
+        raise ValueError(f"{where}: {name} must be {tuple(shape)}, got {tuple(t.shape)}")
+
+
+def _att_scratch(lib, N, H, W, Cin, Cout, dev):
+    nbytes = int(lib.kp2d_att_train_scratch_bytes(N, H, W, Cin, Cout))
+    if nbytes == 0:
+        raise ValueError(f"attention training does not support N {N}, H {H}, W {W}, channels {Cin}, {Cout}")
+    return _dev.scratch(nbytes, dev)
+
+
+def layernorm_forward(x, g, b, eps=LN_EPS):
+    """The reference's channel LayerNorm: x [N, C, H, W], g and b of C elements -> (y, mean, rinv):
+    y = (x - mean) / (sqrt(var_biased) + eps) g + b over the channels of each pixel; mean and rinv = 1 / (sqrt(var) + eps)
+    are [N, H, W], what ``layernorm_backward`` reads."""
+    C = _att_channels(x)
+    N, H, W = _check_att("layernorm_forward", (("x", x, None),), vectors=(("g", g, C), ("b", b, C)))
+    y = torch.empty_like(x)
+    mean = torch.empty(N, H, W, dtype=torch.float32, device=x.device)
+    rinv = torch.empty_like(mean)
+    _lib.check(_lib.load().kp2d_layernorm_forward_train(_ptr(x), _ptr(g.detach()), _ptr(b.detach()), N, C, H, W, float(eps), _ptr(y), _ptr(mean),
+                                                        _ptr(rinv), _stream(x.device)))
+    return y, mean, rinv
+
+
+def layernorm_backward(x, g, mean, rinv, dy, eps=LN_EPS):
+    """-> (dx, dg, db), dg and db shaped like ``g``.  A pixel whose channels are all equal (sqrt(var) = 0) takes the term
+    through the deviation as 0, where torch gives NaN.  Bit-reproducible."""
+    C = _att_channels(x)
+    N, H, W = _check_att("layernorm_backward", (("x", x, None), ("dy", dy, C)), vectors=(("g", g, C),))
+    for name, t in (("mean", mean), ("rinv", rinv)):
+        if not isinstance(t, torch.Tensor) or not _is_device(t) or t.dtype != torch.float32 or tuple(t.shape) != (N, H, W) or not t.is_contiguous():
+            raise ValueError(f"layernorm_backward: {name} must be a contiguous float32 device tensor {(N, H, W)}")
+    _same("layernorm_backward", "dy", dy, x.shape)
+    lib = _lib.load()
+    scratch = _att_scratch(lib, N, H, W, C, C, x.device)
+    dx, dg, db = torch.empty_like(x), torch.empty_like(g.detach()), torch.empty_like(g.detach())
+    _lib.check(lib.kp2d_layernorm_backward(_ptr(x), _ptr(g.detach()), _ptr(mean), _ptr(rinv), _ptr(dy), N, C, H, W, float(eps), _ptr(dx), _ptr(dg),
+                                           _ptr(db), _ptr(scratch), scratch.numel(), _stream(x.device)))
+    return dx, dg, db
+
+
+def pointwise_forward(x, weight, bias=None, gelu=False):
+    """x [N, Cin, H, W], weight [Cout, Cin, 1, 1], bias [Cout] or None -> (y, pre): the 1 x 1 convolution; with ``gelu`` y is
+    nn.GELU()'s exact (erf) form of it and ``pre`` the value before, else ``pre`` is None."""
+    Cin = _att_channels(x)
+    if not isinstance(weight, torch.Tensor) or weight.dim() != 4:
+        raise ValueError("pointwise_forward: weight must be a [Cout, Cin, 1, 1] device tensor")
+    Cout = weight.shape[0]
+    N, H, W = _check_att("pointwise_forward", (("x", x, None),), weights=(("weight", weight, (Cout, Cin, 1, 1)),),
+                         vectors=(("bias", bias, Cout),) if bias is not None else ())
+    if Cout not in ATT_CH:
+        raise ValueError(f"pointwise_forward: Cout {Cout} is not one of {ATT_CH}")
+    y = torch.empty(N, Cout, H, W, dtype=torch.float32, device=x.device)
+    pre = torch.empty_like(y) if gelu else None
+    _lib.check(_lib.load().kp2d_pointwise_forward_train(_ptr(x), _ptr(weight.detach()), _ptr(None if bias is None else bias.detach()), N, H, W,
+                                                        Cin, Cout, int(bool(gelu)), _ptr(y), _ptr(pre), _stream(x.device)))
+    return y, pre
+
+
+def pointwise_backward(x, weight, dy, pre=None, need_dx=True, need_dbias=True):
+    """``pointwise_forward``'s input and weight, the gradient ``dy`` of its ``y`` and, for a call with ``gelu``, its ``pre`` ->
+    (dx or None, dweight [Cout, Cin, 1, 1], dbias [Cout] or None).  Bit-reproducible."""
+    Cin = _att_channels(x)
+    if not isinstance(weight, torch.Tensor) or weight.dim() != 4:
+        raise ValueError("pointwise_backward: weight must be a [Cout, Cin, 1, 1] device tensor")
+    Cout = weight.shape[0]
+    maps = (("x", x, None), ("dy", dy, Cout)) + ((("pre", pre, Cout),) if pre is not None else ())
+    N, H, W = _check_att("pointwise_backward", maps, weights=(("weight", weight, (Cout, Cin, 1, 1)),))
+    for name, t, _ in maps[1:]:
+        _same("pointwise_backward", name, t, (N, Cout, H, W))
+    lib = _lib.load()
+    dev = x.device
+    if pre is not None:
+        dpre = torch.empty_like(dy)
+        _lib.check(lib.kp2d_gelu_backward(_ptr(pre), _ptr(dy), dy.numel(), _ptr(dpre), _stream(dev)))
+        dy = dpre
+    scratch = _att_scratch(lib, N, H, W, Cin, Cout, dev)
+    dx = torch.empty_like(x) if need_dx else None
+    dw = torch.empty_like(weight.detach())
+    db = torch.empty(Cout, dtype=torch.float32, device=dev) if need_dbias else None
+    _lib.check(lib.kp2d_pointwise_backward(_ptr(x), _ptr(weight.detach()), _ptr(dy), N, H, W, Cin, Cout, _ptr(dx), _ptr(dw), _ptr(db),
+                                           _ptr(scratch), scratch.numel(), _stream(dev)))
+    return dx, dw, db
+
+
+def _check_patch2(where, x, weight, dy=None):
+    C = _att_channels(x)
+    N, H, W = _check_att(where, (("x", x, None),), weights=(("weight", weight, (2 * C, C, 2, 2)),), attention=True)
+    if dy is not None:
+        _f32_maps(where, (("dy", dy),))
+        if tuple(dy.shape) != (N, 2 * C, H // 2, W // 2) or dy.device != x.device or not dy.is_contiguous():
+            raise ValueError(f"{where}: dy must be contiguous {(N, 2 * C, H // 2, W // 2)} on {x.device}, got {tuple(dy.shape)}")
+    return N, C, H, W
+
+
+def patch2_forward(x, weight):
+    """``to_kv``: x [N, C, H, W], weight [2 C, C, 2, 2] -> the 2 x 2 stride-2 convolution without padding or bias,
+    [N, 2 C, H // 2, W // 2]; an odd map's last row or column feeds nothing."""
+    N, C, H, W = _check_patch2("patch2_forward", x, weight)
+    y = torch.empty(N, 2 * C, H // 2, W // 2, dtype=torch.float32, device=x.device)
+    _lib.check(_lib.load().kp2d_patch2_forward_train(_ptr(x), _ptr(weight.detach()), N, C, H, W, _ptr(y), _stream(x.device)))
+    return y
+
+
+def patch2_backward(x, weight, dy, need_dx=True):
+    """-> (dx or None, dweight [2 C, C, 2, 2]); the dx of an odd map's last row or column is written as exact zeros."""
+    N, C, H, W = _check_patch2("patch2_backward", x, weight, dy)
+    lib = _lib.load()
+    scratch = _att_scratch(lib, N, H, W, C, 2 * C, x.device)
+    dx = torch.empty_like(x) if need_dx else None
+    dw = torch.empty_like(weight.detach())
+    _lib.check(lib.kp2d_patch2_backward(_ptr(x), _ptr(weight.detach()), _ptr(dy), N, C, H, W, _ptr(dx), _ptr(dw), _ptr(scratch), scratch.numel(),
+                                        _stream(x.device)))
+    return dx, dw
+
+
+def dwconv3_forward(x, weight, bias):
+    """x [N, C, H, W], weight [C, 1, 3, 3], bias [C] -> the depthwise 3 x 3 convolution (padding 1) + bias."""
+    C = _att_channels(x)
+    N, H, W = _check_att("dwconv3_forward", (("x", x, None),), weights=(("weight", weight, (C, 1, 3, 3)),), vectors=(("bias", bias, C),))
+    y = torch.empty_like(x)
+    _lib.check(_lib.load().kp2d_dwconv3_forward_train(_ptr(x), _ptr(weight.detach()), _ptr(bias.detach()), N, C, H, W, _ptr(y), _stream(x.device)))
+    return y
+
+
+def dwconv3_backward(x, weight, dy, need_dx=True):
+    """-> (dx or None, dweight [C, 1, 3, 3], dbias [C]).  Bit-reproducible."""
+    C = _att_channels(x)
+    N, H, W = _check_att("dwconv3_backward", (("x", x, None), ("dy", dy, C)), weights=(("weight", weight, (C, 1, 3, 3)),))
+    _same("dwconv3_backward", "dy", dy, x.shape)
+    lib = _lib.load()
+    scratch = _att_scratch(lib, N, H, W, C, C, x.device)
+    dx = torch.empty_like(x) if need_dx else None
+    dw = torch.empty_like(weight.detach())
+    db = torch.empty(C, dtype=torch.float32, device=x.device)
+    _lib.check(lib.kp2d_dwconv3_backward(_ptr(x), _ptr(weight.detach()), _ptr(dy), N, C, H, W, _ptr(dx), _ptr(dw), _ptr(db), _ptr(scratch),
+                                         scratch.numel(), _stream(x.device)))
+    return dx, dw, db
+
+
+def _check_attention(where, q, kv, others=()):
+    C = _att_channels(q)
+    N, H, W = _check_att(where, (("q", q, None),) + tuple((n, t, C) for n, t in others), attention=True)
+    _f32_maps(where, (("kv", kv),))
+    if tuple(kv.shape) != (N, 2 * C, H // 2, W // 2) or kv.device != q.device or not kv.is_contiguous():
+        raise ValueError(f"{where}: kv must be contiguous {(N, 2 * C, H // 2, W // 2)} on {q.device}, got {tuple(kv.shape)}")
+    for name, t in others:
+        _same(where, name, t, q.shape)
+    return N, C, H, W
+
+
+def attention_forward(q, kv):
+    """q [N, C, H, W], kv [N, 2 C, H // 2, W // 2] (keys, then values) -> (o [N, C, H, W], lse [2, N, 4, H W]): four heads of
+    C / 4 channels, softmax(q k^T (C / 4)^-0.5) v by an online softmax; lse[0] is each query's log-sum-exp of its scaled
+    logits and lse[1] what rounding it to float32 dropped (the backward's probabilities would carry it)."""
+    N, C, H, W = _check_attention("attention_forward", q, kv)
+    o = torch.empty_like(q)
+    lse = torch.empty(2, N, ATT_HEADS, H * W, dtype=torch.float32, device=q.device)
+    _lib.check(_lib.load().kp2d_attention_forward_train(_ptr(q), _ptr(kv), N, C, H, W, _ptr(o), _ptr(lse), _stream(q.device)))
+    return o, lse
+
+
+def attention_backward(q, kv, o, lse, do):
+    """-> (dq like ``q``, dkv like ``kv``).  The probabilities are formed again from q, k and ``lse``; dq is owned by query
+    tiles, dk and dv by key tiles, each walking the other axis in ascending order.  Bit-reproducible."""
+    N, C, H, W = _check_attention("attention_backward", q, kv, (("o", o), ("do", do)))
+    if not isinstance(lse, torch.Tensor) or not _is_device(lse) or lse.dtype != torch.float32 or tuple(lse.shape) != (2, N, ATT_HEADS, H * W) \
+            or not lse.is_contiguous():
+        raise ValueError(f"attention_backward: lse must be a contiguous float32 device tensor {(2, N, ATT_HEADS, H * W)}")
+    lib = _lib.load()
+    scratch = _att_scratch(lib, N, H, W, C, C, q.device)
+    dq, dkv = torch.empty_like(q), torch.empty_like(kv)
+    _lib.check(lib.kp2d_attention_backward(_ptr(q), _ptr(kv), _ptr(o), _ptr(lse), _ptr(do), N, C, H, W, _ptr(dq), _ptr(dkv), _ptr(scratch),
+                                           scratch.numel(), _stream(q.device)))
+    return dq, dkv
+
+
+def attention_module_parameters(module):
+    """A SegFormerAttentionModule's 15 tensors in the reference's registration order (``module.parameters()``'s)."""
+    att, mff = module.att, module.mff
+    net = mff.fn.net
+    return [att.fn.to_q.weight, att.fn.to_kv.weight, att.fn.to_out.weight, att.norm.g, att.norm.b, net[0].weight, net[0].bias,
+            net[1].net[0].weight, net[1].net[0].bias, net[1].net[1].weight, net[1].net[1].bias, net[3].weight, net[3].bias, mff.norm.g,
+            mff.norm.b]
+
+
+def attention_module_forward(module, x):
+    """One SegFormerAttentionModule (LayerNorm, to_q / to_kv, attention, to_out, LayerNorm, 1 x 1, depthwise 3 x 3, 1 x 1, GELU,
+    1 x 1; no residuals) on x [N, C, H, W] -> (y, saved): the stage calls chained; ``saved`` is what the backward reads."""
+    p = attention_module_parameters(module)
+    s = {"x": x}
+    s["n1"], s["mean1"], s["rinv1"] = layernorm_forward(x, p[3], p[4])
+    s["q"] = pointwise_forward(s["n1"], p[0])[0]
+    s["kv"] = patch2_forward(s["n1"], p[1])
+    s["o"], s["lse"] = attention_forward(s["q"], s["kv"])
+    s["a"] = pointwise_forward(s["o"], p[2])[0]
+    s["n2"], s["mean2"], s["rinv2"] = layernorm_forward(s["a"], p[13], p[14])
+    s["h0"] = pointwise_forward(s["n2"], p[5], p[6])[0]
+    s["h1"] = dwconv3_forward(s["h0"], p[7], p[8])
+    s["h2"], s["pre"] = pointwise_forward(s["h1"], p[9], p[10], gelu=True)
+    y = pointwise_forward(s["h2"], p[11], p[12])[0]
+    return y, s
+
+
+def attention_module_backward(module, saved, dy, need_dx=True):
+    """``attention_module_forward``'s ``saved`` and the gradient of its ``y`` -> (the 15 gradients in registration order, dx or
+    None).  The LayerNorm's dx is the sum of the query branch's and the key/value branch's, in that order."""
+    p, s = attention_module_parameters(module), saved
+    g = [None] * 15
+    d, g[11], g[12] = pointwise_backward(s["h2"], p[11], dy)
+    d, g[9], g[10] = pointwise_backward(s["h1"], p[9], d, pre=s["pre"])
+    d, g[7], g[8] = dwconv3_backward(s["h0"], p[7], d)
+    d, g[5], g[6] = pointwise_backward(s["n2"], p[5], d)
+    d, g[13], g[14] = layernorm_backward(s["a"], p[13], s["mean2"], s["rinv2"], d)
+    d, g[2], _ = pointwise_backward(s["o"], p[2], d, need_dbias=False)
+    dq, dkv = attention_backward(s["q"], s["kv"], s["o"], s["lse"], d)
+    dn_q, g[0], _ = pointwise_backward(s["n1"], p[0], dq, need_dbias=False)
+    dn_kv, g[1] = patch2_backward(s["n1"], p[1], dkv)
+    dx, g[3], g[4] = layernorm_backward(s["x"], p[3], s["mean1"], s["rinv1"], dn_q + dn_kv)
+    return g, (dx if need_dx else None)
