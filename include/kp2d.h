@@ -608,6 +608,63 @@ int kp2d_cbr_backward_batchnorm(const float* x, const float* w, const float* gam
                                 float* dx /* may be NULL */, void* scratch, size_t scratch_bytes, void* stream);
 int kp2d_dropout2d_mask(float* drop, int N, int C, double p, uint64_t seed, int64_t step, int layer, void* stream);
 
+/* ---- The multitask place-recognition loss: batch-hard triplet on labelled embeddings (nano-vs-slam_amd/csrc/hard_triplet.hip) ----
+ * The `vlad` term of the reference's train_multitask.py: HardTripletLoss (src/kp2dtiny/utils/losses.py:9-152) on
+ * cat(vlad, vlad_aug) with the labels cat(arange(N), arange(N)) (KeypointNetwithIOLoss.py:572-583, :919-926), forward and
+ * gradient in one call.  Stateless like the calls above: caller-owned device buffers, the caller's stream, no synchronisation,
+ * no float atomics; every argument is checked on the host before the first launch and every output is fully written.
+ *   emb [M, dim] fp32, labels [M] int32 on the device; 1 <= M (else KP2D_ERR_ARG), M <= 512 (else KP2D_ERR_UNSUPPORTED),
+ *     dim >= 1; margin and weight finite, margin >= 0; flags: KP2D_HT_HARDEST | KP2D_HT_SQUARED, nothing else (else
+ *     KP2D_ERR_ARG).  emb, labels, loss, demb 4-byte aligned, stats 8-byte, scratch 16-byte and at least
+ *     kp2d_hard_triplet_scratch_bytes(M, dim) bytes (0: bad shape); a shorter one is KP2D_ERR_ARG.
+ *   -> loss (one float), demb [M, dim] = d loss / d emb, stats [4] int64: anchors with a positive hinge (HARDEST) or hard
+ *     triplets (batch-all), anchors without a positive, anchors without a negative, zero off-diagonal entries of the
+ *     distance matrix (so a pair of equal rows counts twice).
+ *
+ * Distances: D2_ij = sum_k (x_ik - x_jk)^2, the differences of the widened operands (exact) squared and added in float64 in
+ *   ascending k: the reference's max(0, n_i - 2 G_ij + n_j), G = X X^T, n_i = G_ii, without its cancellation.  Two bitwise-equal
+ *   rows give exactly 0, and d_ij and d_ji are one number with one set of bits.  Without SQUARED d_ij = sqrt(D2_ij) where
+ *   D2_ij > 0; a zero entry stays 0 and passes no gradient (the reference's mask trick; relu'(0) = 0 with SQUARED, d = D2);
+ *   the diagonal is always a zero entry.  d_ij is rounded to fp32 once; [M, M] lives in scratch.
+ * KP2D_HT_HARDEST (what the reference's multitask run uses), per anchor a:
+ *       hp_a = max_j d_aj [j != a, label_j = label_a]           (no positive: 0, and no gradient)
+ *       hn_a = min_j (d_aj + rowmax_a [label_j = label_a]),  rowmax_a = max_j d_aj
+ *       loss = weight * mean_a relu(hp_a - hn_a + margin)
+ *   Every max and min takes the lowest index among equal values.  When the minimum lands on a same-label column its gradient
+ *   goes to d_aj and to the row maximum's column: an anchor without any negative has j = a and hn_a = rowmax_a, which is what
+ *   autograd makes of the reference's lines.  (The reference's own hardest branch adds the literal 0.1 and never reads its
+ *   margin; this call takes the margin it is given.)
+ * Batch-all (no KP2D_HT_HARDEST): over triplets with a, p, n distinct and label_p = label_a != label_n,
+ *       h = d_ap - d_an + margin;  loss = weight * sum relu(h) / (count(h > 1e-16) + 1e-16)
+ *   the gradient flows where h > 0; no hard triplet: loss 0 and gradient 0.
+ * Hinges are fp32 arithmetic on the fp32 distances, (d - d') + margin.  They are added in float64 and the loss is rounded once:
+ *   HARDEST one hinge per anchor; batch-all per anchor and negative over the positives in ascending order, then the
+ *   anchor's columns (thread t: columns t and t + 256; lanes by butterfly; the four waves); in both modes the anchors are
+ *   then added the same way.  Counts are exact integers.
+ * Gradient: both modes reduce to INTEGER coefficients c_ij with d loss / d d_ij = scale c_ij, scale = weight / M or
+ *   weight / (count + 1e-16) formed in double and rounded to fp32 (HARDEST: at most three entries per row, +1 at the hardest
+ *   positive, -1 at the minimum's column, -1 at the row maximum's when the minimum is a same-label column; batch-all: the
+ *   active triplets a column takes part in as the positive minus those as the negative).  Then
+ *       demb_i = sum_j s_ij (x_i - x_j),   s_ij = scale (c_ij + c_ji) / d_ij,   with SQUARED  2 scale (c_ij + c_ji)
+ *   over j ascending in fp32 (fma), skipping the terms with c_ij + c_ji = 0, d_ij = 0 or s_ij = 0.  The receiving row scans
+ *   (kp2d_keypoint_loss's rule): no atomics, and a row that no active triplet touches is exactly zero, as is everything
+ *   when plus and minus cancel in c (M = 2 with equal labels: loss = weight * margin, demb = 0).
+ * Edges, as the formulas give them: with SQUARED a D2 above FLT_MAX rounds to inf (so does a distance above it without);
+ *   in batch-all mode hinges with 0 < h <= 1e-16 pass a gradient but are not counted, so when they are the only ones
+ *   scale = weight / 1e-16 (the reference's own quotient).  labels are compared as int32.
+ * Determinism: every sum has a fixed order that depends on (M, dim) alone; all outputs are bit-identical from run to run.
+ *   The mean over anchors couples the rows: a pair run alone does not reproduce its bits of the larger batch.
+ *
+ * The view step of the trainers (nano_vs_slam_amd: NetVLADTrainer.step_views, VPRHeadTrainer.step_views) draws its two
+ * Dropout2d masks with kp2d_dropout2d_mask's counter layout above: layer = 1 for the plain view, as every other step does,
+ * and layer = 2 for the augmented view, at the same seed and step. */
+#define KP2D_HT_HARDEST 1u
+#define KP2D_HT_SQUARED 2u
+size_t kp2d_hard_triplet_scratch_bytes(int M, int dim);
+int kp2d_hard_triplet_loss(const float* emb /* [M, dim] */, const int32_t* labels /* [M], device */, int M, int dim, double margin,
+                           uint32_t flags /* KP2D_HT_HARDEST | KP2D_HT_SQUARED */, double weight, float* loss /* 1 */,
+                           float* demb /* [M, dim] */, int64_t* stats /* [4] */, void* scratch, size_t scratch_bytes, void* stream);
+
 /* ---- Scores of the dense heads: segmentation counts and depth sums (nano-vs-slam_amd/csrc/dense_metrics.hip) -----
  * Replace what the reference's evaluate_segmentation takes from segmentation_models_pytorch (smp.metrics.get_stats,
  * src/evaluation/segmentation.py:42-48) and the reductions inside its compute_errors_torch

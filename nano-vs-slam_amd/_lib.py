@@ -16,6 +16,8 @@ LIB_PATH = os.environ.get("KP2D_LIB") or os.path.join(_HERE, "csrc", "libkp2d_hi
 KP2D_FWD_EVAL = 1
 KP2D_FWD_ONLY_ENCODER = 2
 KP2D_FWD_NO_SEG_LOGITS = 4
+KP2D_HT_HARDEST = 1
+KP2D_HT_SQUARED = 2
 PRECISIONS = {"fp32": 0, "f16x3": 1}
 GLOBAL_DESCRIPTORS = {"netvlad": 0, "gem": 1, "convap": 2}
 UPSCALE_METHODS = {"pixelshuffle": 0, "convtranspose": 1}
@@ -136,6 +138,8 @@ SIGNATURES = {
                                    [_P, C.c_size_t, _P]),
     "kp2d_cbr_backward_batchnorm": (C.c_int, [_P] * 5 + [C.c_double] + [_P] * 4 + [C.c_int] * 5 + [_P] * 4 + [_P, C.c_size_t, _P]),
     "kp2d_dropout2d_mask": (C.c_int, [_P, C.c_int, C.c_int, C.c_double, C.c_uint64, C.c_int64, C.c_int, _P]),
+    "kp2d_hard_triplet_scratch_bytes": (C.c_size_t, [C.c_int, C.c_int]),
+    "kp2d_hard_triplet_loss": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_double, C.c_uint32, C.c_double, _P, _P, _P, _P, C.c_size_t, _P]),
     "kp2d_conv_bias_scratch_bytes": (C.c_size_t, [C.c_int] * 5),
     "kp2d_conv_bias_forward_train": (C.c_int, [_P] * 3 + [C.c_int] * 5 + [_P, _P, C.c_size_t, _P]),
     "kp2d_conv_bias_backward": (C.c_int, [_P] * 3 + [C.c_int] * 5 + [_P] * 3 + [_P, C.c_size_t, _P]),

@@ -13,7 +13,7 @@ import sys
 from concurrent.futures import ThreadPoolExecutor
 
 HERE = os.path.dirname(os.path.abspath(__file__))
-SOURCES = ["conv3x3.hip", "conv3x3_f16.hip", "conv3x3_wsm.hip", "conv3x3_s16.hip", "conv3x3_s16_ids.hip", "head3x3.hip", "netvlad.hip", "post.hip", "attention.hip", "mff_tail.hip", "match.hip", "vpr.hip", "kmeans.hip", "mining.hip", "vlad_train.hip", "vpr_head_train.hip", "seg_train.hip", "depth_train.hip", "keypoint_train.hip", "attention_train.hip", "augment.hip", "dense_metrics.hip", "keypoint_metrics.hip", "lightglue.hip", "model_desc.cpp", "options.cpp",
+SOURCES = ["conv3x3.hip", "conv3x3_f16.hip", "conv3x3_wsm.hip", "conv3x3_s16.hip", "conv3x3_s16_ids.hip", "head3x3.hip", "netvlad.hip", "post.hip", "attention.hip", "mff_tail.hip", "match.hip", "vpr.hip", "kmeans.hip", "mining.hip", "vlad_train.hip", "hard_triplet.hip", "vpr_head_train.hip", "seg_train.hip", "depth_train.hip", "keypoint_train.hip", "attention_train.hip", "augment.hip", "dense_metrics.hip", "keypoint_metrics.hip", "lightglue.hip", "model_desc.cpp", "options.cpp",
            "plan.cpp", "kp2d_api.cpp", "lightglue_desc.cpp", "lightglue_plan.cpp", "lightglue_api.cpp"]
 HEADERS = ["kp2d_kernels.h", "api_common.h", "model_desc.h", "weight_table.h", "weight_upload.h", "f16_host.h", "lightglue_desc.h", "lightglue_plan.h", "options.h", "plan.h", "conv_args.h", "conv_policy.h", "attention_form.h", "lightglue_form.h", "select_form.h", "device_guard.h", "device_logic.h", "train_common.h", "train_conv.h", "mix64.h", "conv_common.h", "conv_epilogue.inc", "conv3x3_s16_kernel.inc", os.path.join("..", "..", "include", "kp2d.h"),
            os.path.join("..", "..", "include", "kp2d_lightglue.h")]

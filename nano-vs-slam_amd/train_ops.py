@@ -9,8 +9,11 @@
 * ``layernorm_*``, ``pointwise_*``, ``patch2_*``, ``dwconv3_*``, ``attention_*`` and ``attention_module_forward`` /
   ``attention_module_backward`` — the stages of the attention head's SegFormerAttentionModule (csrc/attention_train.hip).
 * ``adam_step`` (csrc/vlad_train.hip) and ``AdamTrainer``, the base of every trainer: settings, moments, the one update loop.
+* ``hard_triplet_loss`` / ``HardTripletLoss`` / ``view_labels`` (csrc/hard_triplet.hip) — the multitask run's batch-hard triplet
+  loss on view pairs, the one loss two trainers step on (``NetVLADTrainer`` and ``VPRHeadTrainer``); ``vlad_training`` is where
+  callers import it from.
 
-The losses and the NetVLAD layer calls stay with their trainers.  The two styles of refusal stay as they were: the cbr calls and
+The other losses and the NetVLAD layer calls stay with their trainers.  The two styles of refusal stay as they were: the cbr calls and
 ``adam_step`` raise RuntimeError for a CPU tensor (``_dev.require_device``), the others ValueError (``_is_device``, the one
 place that says what a device tensor is).  Every check runs before the library is loaded.
 """
@@ -180,6 +183,88 @@ class AdamTrainer:
             adam_step(p.data, g.view(p.shape), m, v, self.steps, self.lr, self.betas, self.eps)
             with torch.no_grad():     # ``p.data`` counts versions on its own: bump the parameter's, which the engine watches
                 torch.autograd.graph.increment_version(p)       # (_weights_signature: it re-packs its weights)
+
+
+# ---- the view loss of the two place-recognition trainers -----------------------------------------------------------------
+MAX_HT_ROWS = 512
+QUIRK_MARGIN = 0.1      # what the reference's hardest branch adds, whatever margin its HardTripletLoss was built with
+
+
+def view_labels(N, device):
+    """The labels of a batch of N view pairs, rows ordered plain views then augmented views: cat(arange(N), arange(N)) int32."""
+    r = torch.arange(int(N), dtype=torch.int32, device=device)
+    return torch.cat([r, r])
+
+
+def hard_triplet_loss(emb, labels, margin=0.1, hardest=True, squared=False, weight=1.0, scratch=None):
+    """emb [M, dim] float32, labels [M] integers, both on the device, M <= 512 ->
+    (loss [], demb like emb, stats [4] int64): the reference's HardTripletLoss (src/kp2dtiny/utils/losses.py) times
+    ``weight``, with its gradient.  ``hardest``: per anchor the hardest positive against the hardest negative, the mean of
+    relu(hp - hn + margin); else the sum over all valid triplets divided by the number of hard ones.  ``margin`` is used as
+    given in both modes (``HardTripletLoss`` below keeps the reference's quirk).  ``stats``: anchors with a positive hinge
+    (``hardest``) or hard triplets, anchors without a positive, anchors without a negative, zero off-diagonal distances.
+    The formulas, the tie rule (lowest index) and the summation orders are include/kp2d.h's; bit-reproducible.
+    Labels are compared as int32: wider integers must fit its range (they are converted on the device and not read back, so
+    values outside it wrap and two of them may then compare equal)."""
+    for name, t in (("emb", emb), ("labels", labels)):
+        if not isinstance(t, torch.Tensor) or t.device.type != "cuda":
+            raise ValueError(f"hard_triplet_loss: {name} must be a device tensor (there is no CPU path)")
+    if emb.dim() != 2 or emb.dtype != torch.float32 or emb.shape[0] < 1 or emb.shape[1] < 1:
+        raise ValueError(f"emb must be float32 [M, dim], got {emb.dtype} {tuple(emb.shape)}")
+    M, dim = emb.shape
+    if labels.dim() != 1 or labels.numel() != M or labels.is_floating_point() or labels.is_complex() or labels.dtype == torch.bool:
+        raise ValueError(f"labels must be an integer tensor of length {M}, got {labels.dtype} {tuple(labels.shape)}")
+    if M > MAX_HT_ROWS:
+        raise ValueError(f"hard_triplet_loss supports at most {MAX_HT_ROWS} rows, got {M}")
+    if labels.device != emb.device:
+        raise ValueError("emb and labels must live on one device")
+    margin, weight = float(margin), float(weight)
+    if not (0 <= margin < float("inf")) or weight != weight or abs(weight) == float("inf"):
+        raise ValueError(f"margin must be finite and >= 0 and weight finite, got margin {margin}, weight {weight}")
+    emb = emb.detach().contiguous()
+    lab = labels.detach().to(torch.int32).contiguous()      # (labels beyond int32 wrap: see the docstring)
+    lib = _lib.load()
+    dev = emb.device
+    scratch = _dev.scratch(lib.kp2d_hard_triplet_scratch_bytes(M, dim), dev) if scratch is None else scratch
+    loss = torch.empty((), dtype=torch.float32, device=dev)
+    demb = torch.empty_like(emb)
+    stats = torch.empty(4, dtype=torch.int64, device=dev)
+    flags = (_lib.KP2D_HT_HARDEST if hardest else 0) | (_lib.KP2D_HT_SQUARED if squared else 0)
+    _lib.check(lib.kp2d_hard_triplet_loss(_ptr(emb), _ptr(lab), M, dim, margin, flags, weight, _ptr(loss), _ptr(demb), _ptr(stats),
+                                          _ptr(scratch), scratch.numel(), _stream(dev)))
+    return loss, demb, stats
+
+
+class HardTripletLoss:
+    """The reference's class surface: ``crit = HardTripletLoss(margin=0.1, hardest=False, squared=False)``,
+    ``crit(emb, labels)`` -> the loss (a device scalar); ``crit.grad`` and ``crit.stats`` are the gradient with respect to
+    ``emb`` and the ``stats`` of the last call.  The reference's quirk is reproduced: its ``hardest`` branch adds the
+    literal 0.1 and never reads ``self.margin``, so ``hardest=True`` uses 0.1 whatever ``margin`` says (the multitask run
+    builds ``HardTripletLoss(margin=0.5, hardest=True)`` and trains with 0.1).  ``hard_triplet_loss`` takes the margin it
+    is given."""
+
+    def __init__(self, margin=0.1, hardest=False, squared=False):
+        self.margin, self.hardest, self.squared = margin, bool(hardest), bool(squared)
+        self.grad = self.stats = None
+
+    def __call__(self, embeddings, labels):
+        margin = QUIRK_MARGIN if self.hardest else self.margin
+        loss, self.grad, self.stats = hard_triplet_loss(embeddings, labels, margin, self.hardest, self.squared)
+        return loss
+
+    forward = __call__
+
+
+def _views_loss(trainer, N, margin, weight):
+    """-> the view step's ``loss_fn(vlad [2 N, dim], scratch)``; the call's ``stats`` land in ``trainer.ht_stats``.  (The
+    loss takes a scratch of its own: its [2 N, 2 N] matrices need not fit the layer's.)"""
+    if 2 * N > MAX_HT_ROWS:
+        raise ValueError(f"{trainer._WHO}: a view step takes at most {MAX_HT_ROWS // 2} pairs, got {N}")
+
+    def loss_fn(vlad, scratch):
+        loss, dvlad, trainer.ht_stats = hard_triplet_loss(vlad, view_labels(N, vlad.device), margin, True, False, weight)
+        return loss, dvlad
+    return loss_fn
 
 
 # ---- Conv + BatchNorm + (Leaky)ReLU -----------------------------------------------------------------------------------------

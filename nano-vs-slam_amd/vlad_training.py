@@ -6,6 +6,10 @@ kp2d_vlad_backward, kp2d_adam_step; include/kp2d.h).
   ``adam_step`` and the trainers' Adam core (``AdamTrainer``) live in ``train_ops`` and are imported here.
 * ``NetVLADTrainer`` — forward, loss, backward and Adam for ``vlad_head.netvlad.conv.weight`` and
   ``vlad_head.netvlad.centroids`` of a KP2DTiny model; the step's own calls make no host synchronisation.
+* ``hard_triplet_loss`` / ``HardTripletLoss`` / ``view_labels`` — the multitask run's ``vlad`` term, the reference's
+  batch-hard triplet loss on labelled embeddings with its gradient (csrc/hard_triplet.hip, kp2d_hard_triplet_loss; defined in
+  ``train_ops`` beside ``adam_step``, since ``VPRHeadTrainer`` steps on it too), and ``NetVLADTrainer.step_views``, the step that
+  feeds it a batch of view pairs.
 
 Conventions kept from the reference: ``TripletMarginLoss(margin ** 0.5, p=2, reduction="sum")`` divided by the number of
 negatives, rows ordered queries, positives, negatives in query order, ``torch.optim.Adam``'s update.  Stated deviation: only
@@ -22,6 +26,8 @@ import torch
 from . import _dev, _lib
 from ._dev import ptr as _ptr, stream as _stream
 from .train_ops import AdamTrainer, adam_step  # noqa: F401  (adam_step: this module's fourth call, as it always was)
+from .train_ops import MAX_HT_ROWS, QUIRK_MARGIN, HardTripletLoss, _views_loss, hard_triplet_loss, view_labels  # noqa: F401  (the
+#                       view loss: both place-recognition trainers step on it, so it lives with what the trainers share)
 
 MAX_KC = 8192
 
@@ -151,6 +157,8 @@ class NetVLADTrainer(AdamTrainer):
     version counters are bumped, so the engine re-packs its weights on its next call — its ordinary upload path, which goes
     through the host.  ``only_encoder`` is such a call, so a loop over ``step`` pays that upload once per step; the encoder
     being frozen, a loop over ``step_encoded`` on encoder maps computed once does not.
+    ``step_views(frames, frames_aug)`` is the multitask run's step on a batch of view pairs (``augment.view_pair``): the
+    batch-hard triplet loss on (plain views, augmented views) with ``view_labels``; ``ht_stats`` holds its ``stats``.
     GeM / ConvAP poolers and ``remove_netvlad`` models raise ValueError."""
 
     _WHO = "NetVLADTrainer"
@@ -163,6 +171,7 @@ class NetVLADTrainer(AdamTrainer):
         self._init_adam(lr, betas, eps, margin)
         self.model = model
         self.n_active = None          # device int32 scalar of the last step
+        self.ht_stats = None          # device int64 [4] of the last view step
 
     @property
     def layer(self):
@@ -180,13 +189,40 @@ class NetVLADTrainer(AdamTrainer):
 
     def step_encoded(self, enc, B, neg_counts):
         """``enc`` = ``model.only_encoder`` of (queries, positives, negatives) -> the loss before the update."""
+        def loss_fn(vlad, scratch):
+            loss, dvlad, self.n_active = triplet_margin_loss(vlad, B, neg_counts, self.margin, scratch)
+            return loss, dvlad
+        return self._step_layer(enc, loss_fn)
+
+    def _step_layer(self, enc, loss_fn):
+        """The layer's forward on ``enc``, ``loss_fn(vlad, scratch) -> (loss, dvlad)``, backward and one Adam step."""
         weight, cent = self.layer.conv.weight, self.layer.centroids
         x, w, N, S, C, K = _check_layer(enc, weight, cent)
         self._check_contiguous((weight, cent), "the layer's")
         lib = _lib.load()
         scratch = _scratch(lib, N, S, C, K, x.device)
         vlad, saved = netvlad_forward(x, w, cent, scratch)
-        loss, dvlad, self.n_active = triplet_margin_loss(vlad, B, neg_counts, self.margin, scratch)
+        loss, dvlad = loss_fn(vlad, scratch)
         dW, dcent = netvlad_backward(x, w, cent, saved, dvlad, scratch)
         self._apply((weight, cent), (dW, dcent))
         return loss
+
+    def step_views(self, frames, frames_aug, margin=0.1, weight=1.0):
+        """A batch of view pairs, frames and frames_aug [N, 3, H, W] -> the loss before the update:
+        ``weight * hard_triplet_loss(cat(vlad, vlad_aug), view_labels(N), margin, hardest=True)``."""
+        for name, t in (("frames", frames), ("frames_aug", frames_aug)):
+            _dev.require_device(f"NetVLADTrainer.step_views: {name}", t)
+        if frames.dim() != 4 or frames_aug.shape != frames.shape:
+            raise ValueError("frames and frames_aug must both be [N, 3, H, W]")
+        with torch.no_grad():
+            enc = self.model.only_encoder(torch.cat([frames, frames_aug]))
+        N = frames.shape[0]
+        return self.step_views_encoded(enc[:N], enc[N:], margin, weight)
+
+    def step_views_encoded(self, enc, enc_aug, margin=0.1, weight=1.0):
+        """``enc``, ``enc_aug`` = ``model.only_encoder`` of the plain and of the augmented views -> the loss before the update."""
+        for name, t in (("enc", enc), ("enc_aug", enc_aug)):
+            _dev.require_device(f"NetVLADTrainer.step_views_encoded: {name}", t)
+        if enc.dim() != 4 or enc_aug.shape != enc.shape or enc.dtype != torch.float32 or enc_aug.dtype != torch.float32:
+            raise ValueError("enc and enc_aug must both be float32 [N, C, Hc, Wc]")
+        return self._step_layer(torch.cat([enc, enc_aug]), _views_loss(self, enc.shape[0], margin, weight))

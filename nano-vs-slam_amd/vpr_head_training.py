@@ -31,7 +31,8 @@ import torch
 from . import _dev, _lib
 from ._dev import ptr as _ptr, stream as _stream
 from .train_ops import (LEAKY_SLOPE, MAX_CH, MIN_CH, AdamTrainer, _cbr_scratch, adam_step, bn_vectors, cbr_backward,  # noqa: F401
-                        cbr_backward_batch, cbr_forward, cbr_forward_batch, cbr_layer_backward, cbr_layer_forward, dropout2d_scale)
+                        _views_loss, cbr_backward_batch, cbr_forward, cbr_forward_batch, cbr_layer_backward, cbr_layer_forward,
+                        dropout2d_scale)
 from .vlad_training import _check_layer, _scratch as _vlad_scratch, netvlad_backward, netvlad_forward, triplet_margin_loss
 
 
@@ -75,7 +76,9 @@ class VPRHeadTrainer(AdamTrainer):
     The trainer's own calls make no host synchronisation and the loss stays on the device.  After a step every updated parameter's version counter is bumped, so the engine re-packs its
     weights on its next call, re-folding BatchNorm into the packed conv weights through its ordinary upload path;
     ``backbone_features`` is such a call, so a loop over ``step`` pays that upload once per step and a loop over
-    ``step_features`` does not.  GeM / ConvAP poolers and ``remove_netvlad`` models raise ValueError."""
+    ``step_features`` does not.  ``step_views`` / ``step_views_features`` are the multitask run's step on a batch of view
+    pairs, under the batch-hard triplet loss (``vlad_training.hard_triplet_loss``); ``ht_stats`` holds its ``stats``.
+    GeM / ConvAP poolers and ``remove_netvlad`` models raise ValueError."""
 
     _WHO = "VPRHeadTrainer"
 
@@ -97,6 +100,7 @@ class VPRHeadTrainer(AdamTrainer):
             raise ValueError("VPRHeadTrainer: bn='batch' needs a numeric bn.momentum (None, the cumulative average, is not built)")
         self.bn, self.dropout, self.seed = bn, float(dropout), int(seed)
         self.n_active = None          # device int32 scalar of the last step
+        self.ht_stats = None          # device int64 [4] of the last view step
 
     @property
     def layers(self):
@@ -152,47 +156,121 @@ class VPRHeadTrainer(AdamTrainer):
         if feat.dim() != 4 or feat.dtype != torch.float32 or feat.shape[1] != self.layers[0].conv.weight.shape[1]:
             raise ValueError(f"feat must be float32 [N, {self.layers[0].conv.weight.shape[1]}, Hc, Wc], got {feat.dtype} {tuple(feat.shape)}")
         self._check_contiguous(params, "the head's")
-        netvlad = self.model.vlad_head.netvlad
-        weight, cent = netvlad.conv.weight, netvlad.centroids
         lib = _lib.load()
         N, _, H, W = feat.shape
         batch = self.bn == "batch"
         if batch and N * H * W < 2:
             raise ValueError(f"bn='batch' needs more than 1 value per channel, got feat {tuple(feat.shape)}")
-        cmax = max(max(l.conv.weight.shape[:2]) for l in self.layers)
-        scratch = _cbr_scratch(lib, N, H, W, cmax, cmax, feat.device)        # the largest layer's: every layer call fits
+        scratch = self._layer_scratch(lib, feat)
         if drop is None and self.dropout > 0:
             drop = dropout2d_scale(N, self.layers[0].conv.weight.shape[0], self.dropout, self.seed, self.steps + 1, 1, feat.device)
         if batch:
             acts = self._forward_batch(feat.contiguous(), scratch, drop)
         else:
             acts = self.forward_features(feat.contiguous(), scratch, drop)
-        enc = acts[-1][1]
+
+        def loss_fn(vlad, vscratch):
+            loss, dvlad, self.n_active = triplet_margin_loss(vlad, B, neg_counts, self.margin, vscratch)
+            return loss, dvlad
+        return self._finish_step(params, [(acts, drop)], loss_fn, scratch)
+
+    def _layer_scratch(self, lib, feat):
+        N, _, H, W = feat.shape
+        cmax = max(max(l.conv.weight.shape[:2]) for l in self.layers)
+        return _cbr_scratch(lib, N, H, W, cmax, cmax, feat.device)        # the largest layer's: every layer call fits
+
+    def _finish_step(self, params, passes, loss_fn, scratch):
+        """What follows the head's forward: NetVLAD on the maps of ``passes`` = [(acts, drop)], one entry per forward in row
+        order, ``loss_fn(vlad, scratch) -> (loss, dvlad)``, the backward chain of every pass with the passes' parameter
+        gradients added in order, one Adam step and the version bumps (``num_batches_tracked`` rises once per pass)."""
+        netvlad = self.model.vlad_head.netvlad
+        weight, cent = netvlad.conv.weight, netvlad.centroids
+        lib = _lib.load()
+        batch = self.bn == "batch"
+        enc = passes[0][0][-1][1] if len(passes) == 1 else torch.cat([acts[-1][1] for acts, _ in passes])
         x, w, N, S, C, K = _check_layer(enc, weight, cent)
         vscratch = _vlad_scratch(lib, N, S, C, K, x.device)
         vlad, saved = netvlad_forward(x, w, cent, vscratch)
-        loss, dvlad, self.n_active = triplet_margin_loss(vlad, B, neg_counts, self.margin, vscratch)
+        loss, dvlad = loss_fn(vlad, vscratch)
         dW, dcent = netvlad_backward(x, w, cent, saved, dvlad, vscratch)
-        dy = netvlad_backward_input(enc, w, cent, saved, dvlad, vscratch)
-        grads = [None] * 9 + [dW, dcent]
-        for i in (2, 1, 0):
-            layer = self.layers[i]
-            if batch:
-                lx, ly, lc, (mean, invstd) = acts[i]
-                dw, dgamma, dbeta, dy = cbr_backward_batch(lx, layer.conv.weight, layer.bn.weight, mean, invstd, ly, lc, dy, self.slope,
-                                                           drop if i == 0 else None, need_dx=i > 0, scratch=scratch)
-            else:
-                if i == 0 and drop is not None:
-                    dy = dy * drop[:, :, None, None]
-                dw, dgamma, dbeta, dy = cbr_layer_backward(layer, acts[i], dy, self.slope, need_dx=i > 0,
-                                                           scratch=scratch)               # (the backbone is frozen: no dx of layer 1)
-            grads[3 * i:3 * i + 3] = [dw, dgamma, dbeta]
-        self._apply(params, grads)
+        dy_all = netvlad_backward_input(enc, w, cent, saved, dvlad, vscratch)
+        total, row = None, 0
+        for acts, drop in passes:
+            n = acts[0][0].shape[0]
+            dy = dy_all if len(passes) == 1 else dy_all[row:row + n].contiguous()
+            row += n
+            grads = [None] * 9
+            for i in (2, 1, 0):
+                layer = self.layers[i]
+                if batch:
+                    lx, ly, lc, (mean, invstd) = acts[i]
+                    dw, dgamma, dbeta, dy = cbr_backward_batch(lx, layer.conv.weight, layer.bn.weight, mean, invstd, ly, lc, dy, self.slope,
+                                                               drop if i == 0 else None, need_dx=i > 0, scratch=scratch)
+                else:
+                    if i == 0 and drop is not None:
+                        dy = dy * drop[:, :, None, None]
+                    dw, dgamma, dbeta, dy = cbr_layer_backward(layer, acts[i], dy, self.slope, need_dx=i > 0,
+                                                               scratch=scratch)               # (the backbone is frozen: no dx of layer 1)
+                grads[3 * i:3 * i + 3] = [dw, dgamma, dbeta]
+            total = grads if total is None else [a + b for a, b in zip(total, grads)]
+        self._apply(params, total + [dW, dcent])
         if batch:
             with torch.no_grad():     # the kernel wrote the running statistics through their addresses: bump those too
                 for layer in self.layers:
                     if layer.bn.track_running_stats:
                         torch.autograd.graph.increment_version(layer.bn.running_mean)
                         torch.autograd.graph.increment_version(layer.bn.running_var)
-                        layer.bn.num_batches_tracked.add_(1)
+                        layer.bn.num_batches_tracked.add_(len(passes))
         return loss
+
+    def step_views(self, frames, frames_aug, margin=0.1, weight=1.0):
+        """A batch of view pairs, frames and frames_aug [N, 3, H, W] (``augment.view_pair``) -> the loss before the update."""
+        for name, t in (("frames", frames), ("frames_aug", frames_aug)):
+            _dev.require_device(f"VPRHeadTrainer.step_views: {name}", t)
+        if frames.dim() != 4 or frames_aug.shape != frames.shape:
+            raise ValueError("frames and frames_aug must both be [N, 3, H, W]")
+        with torch.no_grad():
+            feat = self.model.backbone_features(torch.cat([frames, frames_aug]))
+        N = frames.shape[0]
+        return self.step_views_features(feat[:N], feat[N:], margin, weight)
+
+    def step_views_features(self, feat, feat_aug, margin=0.1, weight=1.0, drop=None):
+        """``feat``, ``feat_aug`` = ``model.backbone_features`` of the plain and of the augmented views -> the loss before the
+        update: ``weight * hard_triplet_loss(cat(vlad, vlad_aug), view_labels(N), margin, hardest=True)``, the multitask run's
+        ``vlad`` term.  ``bn="running"``: both views run through ``convlad1..3`` as one batch of 2 N.  ``bn="batch"``: each view
+        is its own forward and backward through the three layers, as the reference's two ``keypoint_net(...)`` calls under
+        ``model.train()``: its own batch statistics, the running statistics moved twice, plain view first,
+        ``num_batches_tracked`` + 2, the two views' parameter gradients added, plain first; NetVLAD and the loss see all 2 N
+        rows.  ``dropout=p``: one mask per view, ``dropout2d_scale(N, C, p, seed, step, 1, device)`` for the plain view and layer
+        id 2 for the augmented one; ``drop=(mask, mask_aug)`` injects both.  ``ht_stats`` holds the loss call's ``stats``."""
+        params = self.parameters()
+        cin = self.layers[0].conv.weight.shape[1]
+        for name, t in (("feat", feat), ("feat_aug", feat_aug)):
+            _dev.require_device(f"VPRHeadTrainer.step_views_features: {name}", t)
+            if t.dim() != 4 or t.dtype != torch.float32 or t.shape[1] != cin:
+                raise ValueError(f"{name} must be float32 [N, {cin}, Hc, Wc], got {t.dtype} {tuple(t.shape)}")
+        if feat_aug.shape != feat.shape:
+            raise ValueError(f"feat and feat_aug must have one shape, got {tuple(feat.shape)} and {tuple(feat_aug.shape)}")
+        self._check_contiguous(params, "the head's")
+        N, _, H, W = feat.shape
+        loss_fn = _views_loss(self, N, margin, weight)
+        batch = self.bn == "batch"
+        if batch and N * H * W < 2:
+            raise ValueError(f"bn='batch' needs more than 1 value per channel, got feat {tuple(feat.shape)}")
+        cout = self.layers[0].conv.weight.shape[0]
+        if drop is not None:
+            if len(drop) != 2 or any(tuple(d.shape) != (N, cout) for d in drop):
+                raise ValueError(f"drop must be (mask, mask_aug), both [{N}, {cout}]")
+        elif self.dropout > 0:
+            drop = tuple(dropout2d_scale(N, cout, self.dropout, self.seed, self.steps + 1, layer, feat.device) for layer in (1, 2))
+        lib = _lib.load()
+        if batch:
+            scratch = self._layer_scratch(lib, feat)
+            passes = [(self._forward_batch(f.contiguous(), scratch, d), d)
+                      for f, d in ((feat, None if drop is None else drop[0]), (feat_aug, None if drop is None else drop[1]))]
+        else:
+            both = torch.cat([feat, feat_aug])
+            d = None if drop is None else torch.cat(list(drop))
+            scratch = self._layer_scratch(lib, both)
+            passes = [(self.forward_features(both, scratch, d), d)]
+        return self._finish_step(params, passes, loss_fn, scratch)
